@@ -45,6 +45,11 @@ KERNEL_NAMES = {"mlp_fwd": "satnerf_fwd2_kernel (one-launch training forward: st
 PMC_ROWS = {"mlp_fwd": "satnerf_fwd", "mlp_bwd": "satnerf_bwd_kernel", "wgrad": "wgrad"}
 PMC_FILE = os.path.join("profiles", "r06_train_pmc.csv")
 MIN_WARM_S = 0.05                 # wall time every leg keeps the device busy before its clock starts (clocks, caches)
+DUMP_WARM_ROUNDS = 20             # --dump-outputs: the MIN_WARM_S loop runs this many rounds of 50 steps instead (the step count, hence the inputs of
+                                  # the dumped step, must not depend on the build's speed); >= 90 ms of work on MI355X, longer than MIN_WARM_S
+DUMP_MAX_BYTES = 64 << 20         # --dump-outputs: larger outputs are written as a fixed, seeded sample of their rows
+MAX_CPU_WORKERS = 4               # cpu_baseline's sharded leg: each worker's first backward() starts the HIP runtime (autograd counts the devices
+                                  # of every backend), so every worker holds the GPU open beside the bench process: at most 5 such processes
 
 
 def pmc_counter(kernel_key, counter):
@@ -108,6 +113,10 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the forward / parity_mode sub-records")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --rays per GPU (the default, what the driver's N = 1, 2, 4, 8 curve measures); strong: --rays in total, rank r takes rays r::N")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step (rank 0) as DIR/<name>.npy (float32 / float64, <= 64 MB in all); "
+                         "the warm-up then runs a fixed number of steps and (train) the last step starts from the seeded initial weights, so the "
+                         "same arguments give the same inputs on every run")
     return ap.parse_args()
 
 
@@ -154,7 +163,8 @@ def cpu_baseline(phase, n_rays, n_samples, budget_s=10.0):
     2.6 rays/s at 256 threads), so the best setting uses 16 of the host's threads;  (b) r06: the batch SHARDED over host_cpus / 16
     processes of 16 threads each (every process renders and back-propagates its slice of the rays, started together) -- all of the host's
     hardware threads at work on one batch (measured: SLOWER than (a), 882 against 2,028 rays/s on a 256-thread host: 64-ray shards are
-    too small for 16 threads).  `value` is the better of the two; both are reported."""
+    too small for 16 threads).  `value` is the better of the two; both are reported.  The fleet is capped at MAX_CPU_WORKERS processes: a
+    worker's backward() opens the GPU, so an uncapped fleet put 17 processes on the device of a 256-thread host."""
     import subprocess
 
     cores = os.cpu_count() or 1
@@ -179,7 +189,7 @@ def cpu_baseline(phase, n_rays, n_samples, budget_s=10.0):
            "single_process": {"value": single, "threads": best_thr, "sweep_rays_per_s": {str(k): round(v, 1) for k, v in sweep.items()}}}
     # (b) the batch sharded over processes
     per = 16 if cores >= 32 else max(cores // 2, 1)
-    procs = max(min(cores // per, n // 8), 1)
+    procs = max(min(cores // per, n // 8, MAX_CPU_WORKERS), 1)
 
     def fleet(rays_each, seconds):
         cmd = [sys.executable, os.path.abspath(__file__), "--cpu-worker", phase, str(rays_each), str(n_samples), str(per), str(seconds)]
@@ -212,8 +222,9 @@ def cpu_baseline(phase, n_rays, n_samples, budget_s=10.0):
 
 
 def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, want_kernels=True, bwd_fmt=None, fc_units=None, sc_lambda=0.0,
-            ds_lambda=0.0):
-    """Run one phase in one numeric mode: returns (seconds for `steps` steps on this rank, {kernel: mean ms} from the eager leg)."""
+            ds_lambda=0.0, dump_dir=None):
+    """Run one phase in one numeric mode: returns (seconds for `steps` steps on this rank, {kernel: mean ms} from the eager leg).
+    `dump_dir`: a fixed-length warm-up, and rank 0 writes the outputs of the last timed step there (dump_outputs)."""
     from satnerf_amd import ops, rendering
     from satnerf_amd import train as train_mod
     from satnerf_amd.data import RayBank, default_args, synthetic_rays  # SURVEY.md 8d recipe; oracle/ is only used by cpu_baseline()
@@ -237,6 +248,7 @@ def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, wan
     bank = RayBank(bank_rays.to(dev), bank_rgb.to(dev), bank_ts.to(dev), n_rays, seed=11, rank=rank, world_size=world)
     torch.manual_seed(1234 + rank)  # per-rank sampling jitter
 
+    reset_state = None  # (--dump-outputs, train: run before the last timed step)
     if phase == "train":
         # the reference's schedule is ON (main.py:86-94,128-131): StepLR per epoch and the SNerfLoss warm-up live in the device-side
         # schedule block of the captured step.  The measured steps are those of the main phase: the counter starts after the two
@@ -245,6 +257,18 @@ def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, wan
         stepper = train_mod.Trainer(models, args, world_size=world, steps_per_epoch=spe)
         stepper.n_steps = 2 * spe
         measure.schedule = {"steps_per_epoch": spe, "first_measured_step": stepper.n_steps, "warming_up": bool(stepper.warming_up())}
+        if dump_dir:
+            # float-atomic gradient reductions make every step differ in its last bits from run to run, and Adam carries that far over a
+            # thousand steps: the dumped step starts from the seeded initial weights and zero moments instead (batch, jitter and schedule
+            # already follow from the step count), so its inputs are the same on every run and every build
+            state0 = [t.clone() for t in (stepper.state.params, stepper.exp_avg, stepper.exp_avg_sq)]
+
+            def reset_state():
+                for dst, src in zip((stepper.state.params, stepper.exp_avg, stepper.exp_avg_sq), state0):
+                    dst.copy_(src)
+                for m in stepper.state.modules:
+                    if hasattr(m, "mark_weights_changed"):
+                        m.mark_weights_changed()
 
         depth_bank = None
         if ds_lambda > 0:  # main.py:103-109,134-141: a second shuffled loader of (ray, [target depth, weight]) items, one batch of it per step
@@ -289,12 +313,14 @@ def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, wan
     # ... and keeps the device busy for at least MIN_WARM_S of wall time before the clock starts: after release_leg()'s synchronize +
     # empty_cache the chip has idled and dropped its clocks, and a 4-ms warm-up of 0.09-ms steps timed a cold device (r04's driver-run
     # `forward` read 7.8 M rays/s where the same kernel sustains 12 M)
-    t_warm = time.perf_counter()
-    while time.perf_counter() - t_warm < MIN_WARM_S:
+    t_warm, rounds = time.perf_counter(), 0
+    while rounds < DUMP_WARM_ROUNDS if dump_dir else time.perf_counter() - t_warm < MIN_WARM_S:
         for _ in range(50):
             step()
         torch.cuda.synchronize()
+        rounds += 1
     measure.warm_s = time.perf_counter() - t_warm
+    n_before = PREWARM + warmup + 50 * rounds  # steps before the timed ones
     fence()
     prof = None
     if os.environ.get("BENCH_PROFILE"):  # diagnostic: where the host spends the enqueue time
@@ -303,7 +329,10 @@ def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, wan
         prof = cProfile.Profile()
         prof.enable()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1 if reset_state else steps):
+        step()
+    if reset_state:
+        reset_state()
         step()
     measure.host_enqueue_s = time.perf_counter() - t0  # host time to enqueue the steps (the device runs behind)
     if prof is not None:
@@ -314,6 +343,17 @@ def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, wan
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
+    if dump_dir and rank == 0:
+        # the last timed step, before the eager leg below steps on: what a caller of the step holds now
+        if phase == "train":
+            arrays = {"loss": torch.as_tensor(stepper.last_loss.detach()).double().sum(), "rgb": stepper.last_rgb}
+            arrays.update({f"param.{key}.{name}": p for key in ("coarse", "t") for name, p in models[key].named_parameters()})
+            done = stepper.n_steps - measure.schedule["first_measured_step"]
+        else:
+            arrays = {k: v for k, v in graphed.out.items() if torch.is_tensor(v) and v.is_floating_point()}
+            done = graphed._launches
+        assert done == n_before + steps, (done, n_before, steps)
+        measure.dumped = dict(dump_outputs(dump_dir, arrays), step=done)
     kernels = {}
     if want_kernels:
         # roofline leg: the same step launched eagerly with HIP events around the hot kernels, same process, same data
@@ -337,6 +377,27 @@ def measure(phase, mode, n_rays, n_samples, steps, warmup, world, rank, dev, wan
                               # sr_adam_step_pack: no sr_pack_all, no separate Adam launch)
                               "update_repacks": bool(getattr(stepper, "_pack_in_tail", False))}
     return dt, kernels, fmt
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32 (float64 stays float64).  Past DUMP_MAX_BYTES in all, every array of more
+    than one row keeps the same fraction of its rows, chosen by a fixed seed (sorted): the sample depends on the shapes only."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items() if v is not None}
+    host = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    frac = min(1.0, DUMP_MAX_BYTES / total) if total else 1.0
+    sampled = []
+    for name, v in sorted(host.items()):
+        if frac < 1.0 and v.ndim >= 1 and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * frac))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+            sampled.append(name)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        host[name] = v
+    return {"dir": out_dir, "files": len(host), "bytes": sum(v.nbytes for v in host.values()), "sampled": sampled}
 
 
 def release_leg():
@@ -395,7 +456,7 @@ def main():
         torch.cuda.synchronize()
         comm = {"rccl_ranks": int(round(ones.item())), "backend": dist.get_backend(), "allreduce_us": e0.elapsed_time(e1) / 20 * 1e3,
                 "allreduce_bytes": flat.numel() * 4}
-    dt, kernel_ms, fmt = measure(phase, a.mode, rays_rank, a.samples, a.steps, a.warmup, world, rank, dev)
+    dt, kernel_ms, fmt = measure(phase, a.mode, rays_rank, a.samples, a.steps, a.warmup, world, rank, dev, dump_dir=a.dump_outputs)
     host_enqueue_s = measure.host_enqueue_s
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -442,6 +503,8 @@ def main():
                    "n_samples": a.samples, "parallelism": f"dp{world}"},
         "roofline": roof,
     }
+    if a.dump_outputs:
+        out["dumped"] = measure.dumped  # (step = the dumped step's index in the leg, counting from 1)
     if phase == "train":
         out["schedule"] = measure.schedule      # StepLR + SNerfLoss warm-up are part of the measured step (main.py:86-94,128-131)
     if comm is not None:

@@ -1,8 +1,12 @@
 import os
 import sys
 
-import pytest
-import torch
+# MKL's conditional numerical reproducibility: fp32 GEMMs round the same on every x86 host, Intel or AMD -- the mode the goldens were
+# written in (tests/golden/make_golden.py).  Set before the first MKL call.
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+
+import pytest  # noqa: E402
+import torch  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:

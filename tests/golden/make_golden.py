@@ -28,8 +28,13 @@ import types
 import zipfile
 import zlib
 
-import numpy as np
-import torch
+# MKL's conditional numerical reproducibility: fp32 GEMMs round the same on every x86 host, Intel or AMD (the default dispatch rounds
+# differently per instruction set, and the fine pass magnifies a one-ulp change of the coarse weights past the tests' 1e-6 through
+# sample_pdf); tests/conftest.py sets the same mode.  Set before torch's first MKL call.
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
