@@ -385,6 +385,34 @@ int sr_latlonalt_from_depth(const float* rays, int ray_stride, const float* dept
 int sr_rpc_rays(const double* rpc, int width, int height, double min_alt, double max_alt, const double* center, double range,
                 double sun_elevation_deg, double sun_azimuth_deg, float* rays11, float* rays8, void* stream);
 
+/* ---- DSM extraction: SatelliteDataset.get_dsm_from_nerf_prediction (datasets/satellite.py:277-338) -------------
+ * sr_utm_zone: utm.latlon_to_zone_number + utm.latitude_to_zone_letter as sat_utils.utm_from_latlon uses them (sat_utils.py:105-106),
+ * HOST only: lon normalised to [-180, 180), Norway (zone 32) and Svalbard (31/33/35/37) exceptions, letter = ASCII code of
+ * "CDEFGHJKLMNPQRSTUVWXX"[int(lat + 80) >> 3]; error unless -80 <= lat <= 84 and lon is finite.
+ * sr_utm_from_latlon: sat_utils.utm_from_latlon (sat_utils.py:97-113) for a given zone (1..60): transverse Mercator (Krueger's series
+ * to n^6, WGS84, k0 0.9996, false easting 500 km, false northing 0 in both hemispheres -- the reference's projection string has no
+ * +south), lat / lon degrees (N,) fp64 -> east / north metres (N,) fp64.
+ * sr_depth_to_utm: datasets/satellite.py:292-294 -- sr_latlonalt_from_depth's arithmetic (same `center` = 3 HOST doubles) followed by
+ * the projection above, east / north / alt (N,) fp64.  zone 0 takes the zone of ray 0's point (sat_utils.py:105-106), 1..60 overrides
+ * it; zone_out (2 DEVICE ints) receives {zone number, letter of ray 0's latitude}, number 0 when ray 0's point is unusable (then
+ * east / north are NaN).
+ * sr_dsm_bounds: datasets/satellite.py:303-304 -- bounds (4 DEVICE doubles) = {min east, max east, min north, max north} over the usable
+ * points (finite east, north, alt and |alt| <= 2^20 m), NaN when there are none.
+ * sr_dsm_rasterize: plyflatten(cloud, xoff, yoff, resolution, xsize, ysize, radius, sigma) (datasets/satellite.py:316) by this project's
+ * own convention (not checked against plyflatten): column c covers east [xoff + c r, xoff + (c+1) r), row j
+ * covers north (yoff - (j+1) r, yoff - j r]; each usable in-grid point adds weight w = 1 (sigma = inf) or exp(-d^2 / (2 sigma^2))
+ * (d = cells from the point to the target centre) to every in-grid cell within `radius` (0..4) rows and columns.  dsm (ysize, xsize)
+ * fp32 = sum w alt / sum w (NaN where sum w = 0), weight = sum w.  acc = 2 * xsize * ysize uint64 of caller-owned scratch (64-bit
+ * fixed point, zeroed here): the result is bitwise independent of point order for every sigma. */
+int sr_utm_zone(double lat, double lon, int* zone, int* letter);
+int sr_utm_from_latlon(const double* lat, const double* lon, int64_t n, int zone, double* east, double* north, void* stream);
+int sr_depth_to_utm(const float* rays, int ray_stride, const float* depth, int64_t n_rays, const double* center, double range,
+                    int zone, double* east, double* north, double* alt, int* zone_out, void* stream);
+int sr_dsm_bounds(const double* east, const double* north, const double* alt, int64_t n, double* bounds, void* stream);
+int sr_dsm_rasterize(const double* east, const double* north, const double* alt, int64_t n, double xoff, double yoff,
+                     double resolution, int xsize, int ysize, int radius, double sigma, uint64_t* acc, float* dsm, float* weight,
+                     void* stream);
+
 /* ---- training-step kernels --------------------------------------------------------------
  * sr_satnerf_loss: metrics.SatNerfLoss for the coarse model (metrics.py:21-25,56-73): value = sum of
  * loss_parts[0 .. ceil(N/4)), and grad_scale * dLoss/d{rgb (N,3), weights (N,S), beta (N,S)} in g_*.

@@ -106,6 +106,11 @@ SIGNATURES = {
     "sr_sample_pdf_merge": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp]),
     "sr_sample_pdf": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp]),
     "sr_rpc_rays": (_i, [_vp, _i, _i, _d, _d, _vp, _d, _d, _d, _vp, _vp, _vp]),
+    "sr_utm_zone": (_i, [_d, _d, C.POINTER(_i), C.POINTER(_i)]),
+    "sr_utm_from_latlon": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "sr_depth_to_utm": (_i, [_vp, _i, _vp, _i64, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sr_dsm_bounds": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "sr_dsm_rasterize": (_i, [_vp, _vp, _vp, _i64, _d, _d, _d, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@
 
 #include "adam_device.h"
 #include "ray_device.h"
+#include "geo_device.h"
 
 namespace sr {
 
@@ -165,33 +166,13 @@ __global__ void __launch_bounds__(256) composite_image_kernel(const float* __res
   }
 }
 
-// depth -> scene point -> ECEF -> geodetic, in fp64 (datasets/satellite.py:246-275 + sat_utils.py:76-95): one thread per ray.
+// depth -> scene point -> ECEF -> geodetic, in fp64 (geo_device.h latlonalt_from_ray): one thread per ray.
 __global__ void __launch_bounds__(256) latlonalt_kernel(const float* __restrict__ rays, int ray_stride, const float* __restrict__ depth,
                                                        long n, double cx, double cy, double cz, double range, double* __restrict__ lat,
                                                        double* __restrict__ lon, double* __restrict__ alt) {
-#pragma clang fp contract(off)
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float* r = rays + i * ray_stride;
-  const double d = (double)depth[i];
-  const double x = ((double)r[0] + (double)r[3] * d) * range + cx;
-  const double y = ((double)r[1] + (double)r[4] * d) * range + cy;
-  const double zz = ((double)r[2] + (double)r[5] * d) * range + cz;
-  const double a = 6378137.0, e = 8.1819190842622e-2;
-  const double asq = a * a, esq = e * e;
-  const double b = sqrt(asq * (1 - esq));
-  const double bsq = b * b;
-  const double ep = sqrt((asq - bsq) / bsq);
-  const double p = sqrt(x * x + y * y);
-  const double th = atan2(a * zz, b * p);
-  const double lo = atan2(y, x);
-  const double sth = sin(th), cth = cos(th);
-  const double la = atan2(zz + (ep * ep) * b * (sth * sth * sth), p - esq * a * (cth * cth * cth));
-  const double sla = sin(la);
-  const double N = a / sqrt(1 - esq * (sla * sla));
-  alt[i] = p / cos(la) - N;
-  lon[i] = lo * 180 / 3.141592653589793;
-  lat[i] = la * 180 / 3.141592653589793;
+  latlonalt_from_ray(rays + i * ray_stride, depth[i], cx, cy, cz, range, lat[i], lon[i], alt[i]);
 }
 
 // Closed-form backward (extended with a transparency gradient):

@@ -1,0 +1,177 @@
+"""DSM extraction on the GPU: depth -> UTM point cloud -> rasterised DSM -> Z-registered DSM MAE.
+
+The reference leaves the GPU here and calls pyproj / utm (``sat_utils.utm_from_latlon``), plyflatten
+(``SatelliteDataset.get_dsm_from_nerf_prediction``) and GDAL / rasterio (``sat_utils.dsm_pointwise_diff``).  This module keeps
+their names and argument order; geometry is fp64, the rasteriser is the HIP kernel of csrc/dsm.hip.  No file I/O: GeoTIFF reading
+and writing stay with the caller (``DSM.transform`` is the affine the reference writes).
+
+The rasteriser follows this project's own grid / splat convention (include/satrender.h, sr_dsm_rasterize).  plyflatten cannot be
+run here, so parity with it is not claimed.
+"""
+from __future__ import annotations
+
+import dataclasses
+import math
+
+import torch
+
+from . import ops
+
+
+# ---- grid geometry (host) -------------------------------------------------------------------------------------------------------
+def grid_from_bounds(xmin, xmax, ymin, ymax, resolution):
+    """(xoff, yoff, xsize, ysize) of the grid around a cloud's bounds, as datasets/satellite.py:302-307 sizes it."""
+    r = float(resolution)
+    xoff = math.floor(xmin / r) * r
+    xsize = int(1 + math.floor((xmax - xoff) / r))
+    yoff = math.ceil(ymax / r) * r
+    ysize = int(1 - math.floor((ymin - yoff) / r))
+    return xoff, yoff, xsize, ysize
+
+
+def grid_from_roi(roi):
+    """(xoff, yoff, xsize, ysize, resolution) of an ``{aoi}_DSM.txt`` array (x, y, s, r), with the reference's ``yoff += s * r``
+    (datasets/satellite.py:295-300): (x, y) is the lower-left corner, the grid's row 0 is its top."""
+    vals = [float(v) for v in (roi.tolist() if hasattr(roi, "tolist") else roi)]
+    if len(vals) != 4:
+        raise ValueError(f"roi must hold the 4 values (x, y, s, r) of {{aoi}}_DSM.txt, got {len(vals)}")
+    xoff, yoff, size, r = vals
+    size = int(size)
+    return xoff, yoff + size * r, size, size, r
+
+
+def zone_string(number, letter):
+    return f"{number}{letter}"
+
+
+def utm_zone(lat, lon):
+    """(zone number, band letter) of one point: the utm package's latlon_to_zone_number / latitude_to_zone_letter (lon normalised to
+    [-180, 180), Norway and Svalbard exceptions).  Raises ValueError unless -80 <= lat <= 84 and lon is finite."""
+    try:
+        return ops.utm_zone(lat, lon)
+    except RuntimeError as exc:
+        raise ValueError(str(exc)) from None
+
+
+def _zone_number(zone):
+    z = int(zone) if not isinstance(zone, str) else int("".join(ch for ch in zone if ch.isdigit()) or 0)
+    if not 1 <= z <= 60:
+        raise ValueError(f"UTM zone must be in 1..60, got {zone!r}")
+    return z
+
+
+# ---- public API -----------------------------------------------------------------------------------------------------------------
+def utm_from_latlon(lats, lons, zone=None):
+    """``sat_utils.utm_from_latlon`` (sat_utils.py:97-113) on the GPU: (easts, norths) fp64 device tensors.  The zone is the first
+    point's (as in the reference) unless ``zone`` (1..60 or e.g. "17R") is given.  False northing is 0 in both hemispheres (the
+    reference's "+proj=utm +zone=<n><L>" has no +south): southern points get negative northings."""
+    if not (torch.is_tensor(lats) and torch.is_tensor(lons) and lats.is_cuda and lons.is_cuda):
+        raise ValueError("lats / lons must be GPU tensors: satnerf_amd has no CPU path")
+    lats, lons = lats.reshape(-1).double(), lons.reshape(-1).double()
+    if zone is None:
+        if lats.numel() == 0:
+            raise ValueError("no points: the UTM zone comes from the first point")
+        zone = utm_zone(lats[0].item(), lons[0].item())[0]
+    return ops.utm_from_latlon(lats, lons, _zone_number(zone))
+
+
+@dataclasses.dataclass
+class DSM:
+    """A rasterised DSM.  ``dsm`` is (ysize, xsize) fp32 on the device, NaN where no point landed (the reference's plyflatten returns
+    (h, w, 1) and writes ``[:, :, 0]``); ``weight`` the per-cell sum of splat weights (the point count for sigma = inf).  Cell (j, c)
+    covers east [xoff + c r, xoff + (c+1) r) and north (yoff - (j+1) r, yoff - j r]."""
+    dsm: torch.Tensor
+    weight: torch.Tensor
+    xoff: float
+    yoff: float
+    resolution: float
+    zone: str
+    roi: tuple | None = None
+
+    @property
+    def transform(self):
+        """The GeoTIFF affine (a, b, c, d, e, f) = (r, 0, xoff, 0, -r, yoff) (datasets/satellite.py:333)."""
+        return (self.resolution, 0.0, self.xoff, 0.0, -self.resolution, self.yoff)
+
+
+def dsm_from_depth(rays, depth, center, scene_range, roi=None, resolution=0.5, radius=1, sigma=float("inf"), zone=None):
+    """``SatelliteDataset.get_dsm_from_nerf_prediction`` (datasets/satellite.py:277-338) without file I/O.
+
+    rays (N, >=6) fp32 and depth (N,) or (N, 1) fp32 on the GPU; ``center`` (3,) / ``scene_range`` the dataset's ECEF normalisation.
+    ``roi`` = the (x, y, s, r) array of ``{aoi}_DSM.txt`` (its r replaces ``resolution``); without it the grid spans the cloud.
+    ``radius`` in 0..4, ``sigma`` > 0 or inf (plyflatten's arguments; the reference uses 1 and inf).  Points that are not finite, or
+    outside the grid, contribute nothing.  Returns a :class:`DSM`; the raster is bitwise reproducible and independent of point order."""
+    if not (torch.is_tensor(rays) and torch.is_tensor(depth) and rays.is_cuda and depth.is_cuda):
+        raise ValueError("rays / depth must be GPU tensors: satnerf_amd has no CPU path")
+    if rays.dim() != 2 or rays.shape[1] < 6 or depth.numel() != rays.shape[0]:
+        raise ValueError(f"rays must be (N, >=6) with one depth per ray, got {tuple(rays.shape)} and {tuple(depth.shape)}")
+    if not 0 <= int(radius) <= 4:
+        raise ValueError(f"radius must be in 0..4, got {radius}")
+    if not float(sigma) > 0:
+        raise ValueError(f"sigma must be > 0 or inf, got {sigma}")
+    rays = rays if rays.dtype == torch.float32 and rays.stride(-1) == 1 else rays.float().contiguous()
+    depth = depth.reshape(-1).float().contiguous()
+    zone_in = 0 if zone is None else _zone_number(zone)
+    east, north, alt, zone_out = ops.depth_to_utm(rays, depth, center, scene_range, zone_in)
+    n = rays.shape[0]
+    if roi is not None:
+        xoff, yoff, xsize, ysize, resolution = grid_from_roi(roi)
+        meta = zone_out.cpu().tolist()  # the zone string
+        if xsize < 1 or resolution <= 0:
+            raise ValueError(f"zero-size DSM grid from roi {list(roi)}")
+    else:
+        if n == 0:
+            raise ValueError("no rays: the DSM grid cannot be sized without a roi")
+        # one device-to-host copy: the four bounds (fp64) and the zone (2 int32) side by side
+        buf = torch.empty(5, dtype=torch.int64, device=rays.device)
+        ops.dsm_bounds(east, north, alt, out=buf[:4].view(torch.float64))
+        buf[4:].view(torch.int32).copy_(zone_out)
+        host = buf.cpu()
+        xmin, xmax, ymin, ymax = host[:4].view(torch.float64).tolist()
+        meta = host[4:].view(torch.int32).tolist()
+        if not all(math.isfinite(v) for v in (xmin, xmax, ymin, ymax)):
+            raise ValueError("zero-size DSM grid: no usable point")
+        xoff, yoff, xsize, ysize = grid_from_bounds(xmin, xmax, ymin, ymax, resolution)
+    if n > 0 and meta[0] == 0:
+        raise ValueError("the first ray's point is not finite or lies outside latitudes [-80, 84]: pass zone= explicitly")
+    dsm, weight = ops.dsm_rasterize(east, north, alt, xoff, yoff, resolution, xsize, ysize, int(radius), float(sigma))
+    number = meta[0] or zone_in
+    zone_str = zone_string(number, chr(meta[1]) if meta[1] else "") if number else ""  # "" only for zero rays without zone=
+    return DSM(dsm, weight, float(xoff), float(yoff), float(resolution), zone_str, None if roi is None else tuple(float(v) for v in roi))
+
+
+def dsm_mae(pred, gt, gt_mask=None):
+    """Z-only registration of ``sat_utils.dsm_pointwise_diff`` (sat_utils.py:162-171, the branch taken without dsmr): water cells
+    (mask class 9) become NaN in ``pred``, shift = nanmean(gt - pred), rdsm = pred + shift, err = rdsm - gt, mae = nanmean(|err|).
+
+    ``pred`` is a :class:`DSM` built with ``roi=`` or a (H, W) device tensor already on the ground truth's grid; ``gt`` (H, W) and
+    ``gt_mask`` (H, W) live on the same device.  No cropping (the reference's gdal.Translate) happens here.  Arithmetic is fp64.
+    Returns (mae, err, rdsm, shift): mae / shift as floats, err / rdsm as fp64 device tensors."""
+    if isinstance(pred, DSM):
+        if pred.roi is None:
+            raise ValueError("pred was not built on the ROI grid: call dsm_from_depth(..., roi=...) (cropping is not implemented)")
+        pred = pred.dsm
+    for name, t in (("pred", pred), ("gt", gt), ("gt_mask", gt_mask)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f"{name} must be a GPU tensor: satnerf_amd has no CPU path")
+    if pred.shape != gt.shape or pred.dim() != 2:
+        raise ValueError(f"pred {tuple(pred.shape)} is not on the ground truth's (H, W) grid {tuple(gt.shape)}")
+    if gt_mask is not None and gt_mask.shape != gt.shape:
+        raise ValueError(f"gt_mask {tuple(gt_mask.shape)} does not match gt {tuple(gt.shape)}")
+    p, g = pred.double().clone(), gt.to(pred.device).double()
+    if gt_mask is not None:
+        p[gt_mask == 9] = float("nan")
+    shift = torch.nanmean(g - p)
+    rdsm = p + shift
+    err = rdsm - g
+    mae = torch.nanmean(err.abs())
+    return mae.item(), err, rdsm, shift.item()
+
+
+def render_dsm(models, rays, ts, args, center, scene_range, **dsm_kwargs):
+    """The create_satnerf_dsm flow in one call: ``render_image_outputs(...)["depth"]`` -> :func:`dsm_from_depth`."""
+    from .rendering import render_image_outputs
+
+    with torch.no_grad():
+        depth = render_image_outputs(models, rays, ts, args)["depth"]
+    return dsm_from_depth(rays, depth, center, scene_range, **dsm_kwargs)

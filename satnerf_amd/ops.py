@@ -690,3 +690,62 @@ def adam_step_graph(params, grads, exp_avg, exp_avg_sq, state, lr=5e-4, betas=(0
     _lib.call("sr_adam_step_graph", _p(_chk(params, "params")), _p(_chk(grads, "grads")), _p(_chk(exp_avg, "exp_avg")), _p(_chk(exp_avg_sq, "exp_avg_sq")),
               params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(grad_scale), _p(_chk(state, "state")), int(zero_grad),
               _stream())
+
+
+# ---- DSM extraction (csrc/dsm.hip) ----------------------------------------------------------------------------------------------------
+def utm_zone(lat, lon):
+    """(zone number, band letter) of one point by the utm package's rules (sr_utm_zone, host only); raises unless -80 <= lat <= 84."""
+    zone, letter = C.c_int(0), C.c_int(0)
+    _lib.call("sr_utm_zone", float(lat), float(lon), C.byref(zone), C.byref(letter))
+    return zone.value, chr(letter.value)
+
+
+def utm_from_latlon(lats, lons, zone):
+    """(east, north) fp64 device tensors of fp64 device lat / lon (degrees) in UTM zone ``zone`` (1..60)."""
+    lats, lons = _chk(lats.contiguous(), "lats", torch.float64), _chk(lons.contiguous(), "lons", torch.float64)
+    if lats.dim() != 1 or lats.shape != lons.shape:
+        raise ValueError(f"lats / lons must be two (N,) tensors, got {tuple(lats.shape)} / {tuple(lons.shape)}")
+    out = torch.empty(2, lats.shape[0], dtype=torch.float64, device=lats.device)
+    _lib.call("sr_utm_from_latlon", _p(lats), _p(lons), lats.shape[0], int(zone), out[0].data_ptr(), out[1].data_ptr(), _stream())
+    return out[0], out[1]
+
+
+def depth_to_utm(rays, depth, center, scene_range, zone=0):
+    """(east, north, alt) fp64 device tensors of the points rays_o + rays_d * depth, and a (2,) int32 device tensor {zone number,
+    letter code} of ray 0's point (zone > 0 overrides the number; number 0 = ray 0's point is unusable)."""
+    rays, stride = _rows(rays, "rays", 6)
+    n = rays.shape[0]
+    if depth.reshape(-1).shape[0] != n:
+        raise ValueError("depth must have one value per ray")
+    depth = _chk(depth.reshape(-1).contiguous(), "depth")
+    c = (C.c_double * 3)(*[float(v) for v in center])
+    out = torch.empty(3, n, dtype=torch.float64, device=rays.device)
+    zone_out = torch.zeros(2, dtype=torch.int32, device=rays.device)
+    _lib.call("sr_depth_to_utm", _p(rays), stride, _p(depth), n, C.addressof(c), float(scene_range), int(zone), out[0].data_ptr(),
+              out[1].data_ptr(), out[2].data_ptr(), _p(zone_out), _stream())
+    return out[0], out[1], out[2], zone_out
+
+
+def dsm_bounds(east, north, alt, out=None):
+    """(4,) fp64 device tensor {min east, max east, min north, max north} over the usable points (NaN if none); ``out`` may be given."""
+    east, north, alt = (_chk(t, k, torch.float64) for t, k in ((east, "east"), (north, "north"), (alt, "alt")))
+    if not (east.dim() == 1 and east.shape == north.shape == alt.shape):
+        raise ValueError("east / north / alt must be three (N,) tensors")
+    out = torch.empty(4, dtype=torch.float64, device=east.device) if out is None else _chk(out, "out", torch.float64)
+    _lib.call("sr_dsm_bounds", _p(east), _p(north), _p(alt), east.shape[0], _p(out), _stream())
+    return out
+
+
+def dsm_rasterize(east, north, alt, xoff, yoff, resolution, xsize, ysize, radius=1, sigma=float("inf")):
+    """(dsm, weight) fp32 (ysize, xsize) device tensors: the splat rasteriser of sr_dsm_rasterize."""
+    east, north, alt = (_chk(t, k, torch.float64) for t, k in ((east, "east"), (north, "north"), (alt, "alt")))
+    if not (east.dim() == 1 and east.shape == north.shape == alt.shape):
+        raise ValueError("east / north / alt must be three (N,) tensors")
+    if xsize < 1 or ysize < 1:
+        raise ValueError(f"empty DSM grid ({ysize} x {xsize})")
+    acc = torch.empty(ysize, xsize, 2, dtype=torch.int64, device=east.device)
+    dsm = torch.empty(ysize, xsize, dtype=torch.float32, device=east.device)
+    weight = torch.empty_like(dsm)
+    _lib.call("sr_dsm_rasterize", _p(east), _p(north), _p(alt), east.shape[0], float(xoff), float(yoff), float(resolution), int(xsize),
+              int(ysize), int(radius), float(sigma), _p(acc), _p(dsm), _p(weight), _stream())
+    return dsm, weight
