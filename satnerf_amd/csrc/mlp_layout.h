@@ -220,4 +220,16 @@ __device__ __forceinline__ float wg_sum_slices(const float* __restrict__ partial
 #endif
 
 }  // inline namespace SR_FEAT_NS
+
+// ---- which 8-bit weight-gradient kernel runs (sr_satnerf_wgrad8, planned by sr_wgrad_plan) -------------------------------------------------
+// The 4-wave kernel (wgrad9.hip) unless SATNERF_WGRAD_V1=1 or a workspace exceeds its 32-bit per-lane offsets: then the r02 kernel
+// (wgrad8.hip).  The planner knows neither width nor tau, so it checks the offsets for kWg9PlanUnits 1-KiB units per tile, a bound on
+// the units per tile of both SR_FMT8 workspaces at either width (tests/test_cabi.py).
+// ADVICE r06, kept (fixing it changes plans): past that bound the planner still weights thin blocks, which the r02 kernel runs as full ones.
+constexpr int kWg9PlanUnits = 208;
+constexpr bool wgrad9_fits(long n_tiles, int ak = kWg9PlanUnits, int dk = kWg9PlanUnits) {
+  return n_tiles * (ak > dk ? ak : dk) * 1024l < (1l << 32);
+}
+bool wgrad_v1();  // SATNERF_WGRAD_V1=1, read once per process (wgrad8.hip)
+
 }  // namespace sr

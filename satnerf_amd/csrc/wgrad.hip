@@ -230,11 +230,43 @@ __global__ void __launch_bounds__(256) unpack_grads_kernel(const float* __restri
 
 using namespace sr;
 
-// Split-K plan (host): slices per job block, written into the table together with each block's first slice number.
-// Measured on MI355X (profiles/r01_ab_variants.txt): a workgroup's time per 32-point tile is set by the per-tile latency chain
-// (LDS-DMA landed -> decode -> rendezvous -> transposed reads -> MFMA), 1.0-1.2 us for narrow head blocks and full
-// 256 x 256 blocks alike, so equal slices for every block beat slices in proportion to the fragments moved (195 vs 282 us at
-// 65,536 points), and n_blocks * floor(n_wg / n_blocks) <= n_wg workgroups keeps the launch to one round of workgroups.
+namespace {
+// Greedy cost-weighted split: every block starts with one slice and each further workgroup goes to the block whose workgroups would otherwise
+// finish last, which minimises max_b cost_b * ceil(tiles / slices_b); a block never gets more slices than it has tiles.  Returns that maximum.
+double split_by_cost(const double* cost, int n_blocks, long n_tiles, int n_wg, int* sl) {
+  auto finish = [&](int b) { return cost[b] * (double)((n_tiles + sl[b] - 1) / sl[b]); };
+  for (int b = 0; b < n_blocks; ++b) sl[b] = 1;
+  for (int left = n_wg - n_blocks; left > 0; --left) {
+    int worst = -1;
+    double wt = -1;
+    for (int b = 0; b < n_blocks; ++b)
+      if (finish(b) > wt && sl[b] < n_tiles) wt = finish(b), worst = b;
+    if (worst < 0) break;
+    ++sl[worst];
+  }
+  double makespan = 0;
+  for (int b = 0; b < n_blocks; ++b) makespan = finish(b) > makespan ? finish(b) : makespan;
+  return makespan;
+}
+}  // namespace
+
+// Split-K plan (host): slices per job block, written into the table together with each block's first slice number.  Strategies:
+//   uniform (SR_FMT16, or more blocks than workgroups): n_wg / n_blocks slices for every block (one round of workgroups).  Measured on
+//     MI355X (profiles/r01_ab_variants.txt): the 16-bit kernel's time per 32-point tile is set by its per-tile latency chain, 1.0-1.2 us
+//     for narrow head blocks and full blocks alike, so equal slices beat slices in proportion to the fragments moved (195 vs 282 us);
+//   weighted, r02 kernel (SATNERF_WGRAD_V1=1): a block's time per tile grows with the fragments it decodes, cost = ca + cb * row fragments
+//     + cc * column fragments (relative; MI355X A/B in profiles/r02_ab_variants.txt);
+//   equal, 4-wave kernel (the default): it runs ONE instruction stream for every block -- narrow blocks contract stale operands -- so a tile
+//     costs the same whatever the block: equal slices, the remainder to the first blocks (what wgrad9.hip's workgroup numbering assumes);
+//   weighted, 4-wave kernel (r06): blocks whose row operand is one raw bf16 fragment (head rows: 1 row fragment, PHASE8 columns) run THIN
+//     streams (gen/wgrad9_loop.py THIN, packing.wgrad9_thin_blocks), a tile of theirs costs a fraction of a full block's (tools/ab_wgrad8.py
+//     on sub-tables, profiles/r06_ab_variants.txt) -- unless stream-K is shorter still (width 512's 47 blocks);
+//   stream-K, 4-wave kernel (r05): when equal slices leave the workgroups unevenly loaded (width 512: 47 blocks over 256 workgroups = 5 or 6
+//     slices, 410 against 342 tiles), the job list as one line of n_blocks x n_tiles tile units, `span` consecutive units per workgroup; a
+//     workgroup that crosses a block boundary writes two partial blocks (wgrad9.hip).  Block b's slices = the workgroups whose span touches it.
+// Overrides: SATNERF_WGRAD_STREAMK = 1 / 0 forces stream-K / the weighted or equal split (A/B); SATNERF_WGRAD_THIN=0 (full streams
+// everywhere, packing reads the same switch) makes every block cost 1; SATNERF_WGRAD_THIN_COST="c16,c8" sets the thin costs;
+// SR_PLAN_ENV builds: SR_WGRAD_UNIFORM (slices per block of the uniform plan), SR_WGRAD_COST="ca,cb,cc".
 extern "C" int sr_wgrad_plan(int32_t* blocks, int n_blocks, int64_t n_points, int n_wg, int fmt, int* n_slices) {
   SR_REQUIRE(blocks && n_slices, "sr_wgrad_plan: null pointer");
   SR_REQUIRE(n_blocks >= 1 && n_blocks <= 4096 && n_points >= 1, "sr_wgrad_plan: bad sizes (%d blocks, %lld points)", n_blocks, (long long)n_points);
@@ -247,120 +279,67 @@ extern "C" int sr_wgrad_plan(int32_t* blocks, int n_blocks, int64_t n_points, in
     n_wg = cus;
   }
   const long n_tiles = (n_points + 31) / 32;
-  long per_block = n_wg / n_blocks;
-  per_block = per_block < 1 ? 1 : per_block > n_tiles ? n_tiles : per_block;
-#ifdef SR_PLAN_ENV
-  if (const char* e = getenv("SR_WGRAD_UNIFORM")) per_block = atoi(e);
-#endif
-  // cost-weighted split (fmt 8): a block's time per tile grows with the fragments it decodes, so slices are handed out greedily
-  // to the block whose workgroups would otherwise finish last: minimises max_b cost_b * ceil(tiles / slices_b)
-  // cost of a tile of a block = ca + cb * row fragments + cc * column fragments (relative; MI355X A/B in profiles/r02_ab_variants.txt)
-  double ca = 0.4, cb = 0.02, cc = 0.0175;
-  // the 4-wave kernel (wgrad9.hip, the default) runs ONE instruction stream for every block -- narrow blocks contract stale operands --
-  // so a tile costs the same whatever the block: equal slices (the remainder goes to the first blocks)
-  static const bool old_kernel = [] {
-    const char *a = getenv("SATNERF_WGRAD_V1"), *b = getenv("SATNERF_WGRAD_V2");
-    return (a && a[0] == '1') || (b && b[0] == '1');
-  }();
-  if (!old_kernel) ca = 1.0, cb = 0.0, cc = 0.0;
-#ifdef SR_PLAN_ENV
-  if (const char* e = getenv("SR_WGRAD_COST")) sscanf(e, "%lf,%lf,%lf", &ca, &cb, &cc);
-#endif
-  int first = 0;
   static thread_local int sl[4096];
-  const bool weighted = fmt == SR_FMT8 && n_blocks <= n_wg;
-  blocks[kWgSpan] = 0;
-  // r06: blocks whose row operand is one raw bf16 fragment (head rows: 1 row fragment, PHASE8 columns) run THIN streams in the 4-wave
-  // kernel (gen/wgrad9_loop.py THIN, packing.wgrad9_thin_blocks): a tile of theirs costs a fraction of a full block's.  Relative costs
-  // measured with tools/ab_wgrad8.py on sub-tables (profiles/r06_ab_variants.txt); SATNERF_WGRAD_THIN_COST="c16,c8" overrides them,
-  // SATNERF_WGRAD_THIN=0 (full streams everywhere, packing reads the same switch) makes every block cost 1 again.
-  double thin16 = 0.5, thin8 = 0.4;
-  bool thin_on = true;
-  if (const char* e = getenv("SATNERF_WGRAD_THIN")) thin_on = e[0] != '0';
-  if (const char* e = getenv("SATNERF_WGRAD_THIN_COST")) sscanf(e, "%lf,%lf", &thin16, &thin8);
-  bool any_thin = false;
-  static thread_local double w9cost[4096];
-  for (int b = 0; b < n_blocks; ++b) {
-    const int32_t* t = blocks + kWgTableInts * b;
-    const int nr = t[1] + t[3], nc = t[5] + t[7];
-    const bool thin = thin_on && nr == 1 && t[8] == 1 && (nc == 8 || nc == 16);
-    w9cost[b] = thin ? (nc == 16 ? thin16 : thin8) : 1.0;
-    any_thin |= thin && w9cost[b] != 1.0;
-  }
-  bool use_weights = false;
-  if (weighted && !old_kernel && any_thin && n_blocks <= 64 && n_wg >= n_blocks) {
-    // cost-weighted slices for the 4-wave kernel: greedily to the block whose workgroups would finish last (minimises
-    // max_b cost_b * ceil(tiles / slices_b)); the kernel numbers workgroups slice-major over the blocks that still have slices
-    for (int b = 0; b < n_blocks; ++b) sl[b] = 1;
-    for (int left = n_wg - n_blocks; left > 0; --left) {
-      int worst = -1;
-      double wt = -1;
-      for (int b = 0; b < n_blocks; ++b) {
-        const double tb = w9cost[b] * (double)((n_tiles + sl[b] - 1) / sl[b]);
-        if (tb > wt && sl[b] < n_tiles) wt = tb, worst = b;
-      }
-      if (worst < 0) break;
-      ++sl[worst];
-    }
-    double makespan = 0;
-    for (int b = 0; b < n_blocks; ++b) {
-      const double tb = w9cost[b] * (double)((n_tiles + sl[b] - 1) / sl[b]);
-      makespan = tb > makespan ? tb : makespan;
-    }
-    // ... unless a stream-K plan (below: equal tile spans, thin blocks simply finish early) is shorter still -- width 512's 47 blocks
-    const long span = ((long)n_blocks * n_tiles + n_wg - 1) / n_wg;
-    use_weights = makespan <= (double)span * 1.03 || n_tiles * 208l * 1024l >= (1l << 32);
-    if (const char* e = getenv("SATNERF_WGRAD_STREAMK")) use_weights = e[0] != '1';
-  }
-  if (use_weights) {
-    // (sl[] holds the weighted split)
-  } else if (weighted && !old_kernel) {
-    // equal split, the remainder to the first blocks: what wgrad9.hip's workgroup numbering (slice-major, blocks 8 positions apart on one
-    // XCD) assumes; a block never gets more slices than it has tiles
-    const long q = n_wg / n_blocks, r = n_wg % n_blocks;
-    for (int b = 0; b < n_blocks; ++b) {
-      long v = q + (b < r ? 1 : 0);
-      sl[b] = (int)(v > n_tiles ? n_tiles : v);
-    }
-    // ... unless that leaves the workgroups unevenly loaded (width 512: 47 blocks over 256 workgroups = 5 or 6 slices, 410 against 342
-    // tiles): then stream-K -- the job list as one line of n_blocks x n_tiles tile units, `span` consecutive units per workgroup, a
-    // workgroup that crosses a block boundary writes two partial blocks (wgrad9.hip).  Block b's slices = the workgroups whose span
-    // touches it, numbered in tile order.  SATNERF_WGRAD_STREAMK = 0 / 1 forces the choice (A/B).
-    const long total = (long)n_blocks * n_tiles, span = (total + n_wg - 1) / n_wg;
-    const long worst = q > 0 ? (n_tiles + q - 1) / q : n_tiles;
-    // ... and only where the 4-wave kernel will run it: workspaces it cannot address with 32-bit per-lane offsets (wgrad9_fits; <= 208
-    // 1-KiB units per tile at either width) fall back to the r02 kernel, which takes equal slices only
-    bool streamk = q > 0 && span >= 8 && worst * 100 > span * 103 && n_tiles * 208l * 1024l < (1l << 32);
-    if (const char* e = getenv("SATNERF_WGRAD_STREAMK")) streamk = e[0] == '1' && span >= 1 && n_tiles * 208l * 1024l < (1l << 32);
-    if (streamk) {
-      for (int b = 0; b < n_blocks; ++b) sl[b] = (int)((((long)(b + 1) * n_tiles - 1) / span) - (((long)b * n_tiles) / span) + 1);
-      blocks[kWgSpan] = (int32_t)span;
-    }
-  } else if (weighted) {
-    double cost[4096];
+  static thread_local double cost[4096];
+  long span = 0;
+  if (fmt != SR_FMT8 || n_blocks > n_wg) {
+    long per_block = n_wg / n_blocks;
+    per_block = per_block < 1 ? 1 : per_block > n_tiles ? n_tiles : per_block;
+#ifdef SR_PLAN_ENV
+    if (const char* e = getenv("SR_WGRAD_UNIFORM")) per_block = atoi(e);
+#endif
+    for (int b = 0; b < n_blocks; ++b) sl[b] = (int)per_block;
+  } else if (wgrad_v1()) {
+    double ca = 0.4, cb = 0.02, cc = 0.0175;
+#ifdef SR_PLAN_ENV
+    if (const char* e = getenv("SR_WGRAD_COST")) sscanf(e, "%lf,%lf,%lf", &ca, &cb, &cc);
+#endif
     for (int b = 0; b < n_blocks; ++b) {
       const int32_t* t = blocks + kWgTableInts * b;
       cost[b] = ca + cb * (t[1] + t[3]) + cc * (t[5] + t[7]);
-      sl[b] = 1;
     }
-    for (int left = n_wg - n_blocks; left > 0; --left) {
-      int worst = 0;
-      double wt = -1;
+    split_by_cost(cost, n_blocks, n_tiles, n_wg, sl);
+  } else {
+    double thin16 = 0.5, thin8 = 0.4;
+    bool thin_on = true, any_thin = false;
+    if (const char* e = getenv("SATNERF_WGRAD_THIN")) thin_on = e[0] != '0';
+    if (const char* e = getenv("SATNERF_WGRAD_THIN_COST")) sscanf(e, "%lf,%lf", &thin16, &thin8);
+    for (int b = 0; b < n_blocks; ++b) {
+      const int32_t* t = blocks + kWgTableInts * b;
+      const int nr = t[1] + t[3], nc = t[5] + t[7];
+      const bool thin = thin_on && nr == 1 && t[8] == 1 && (nc == 8 || nc == 16);
+      cost[b] = thin ? (nc == 16 ? thin16 : thin8) : 1.0;
+      any_thin |= thin && cost[b] != 1.0;
+    }
+    const char* streamk_env = getenv("SATNERF_WGRAD_STREAMK");
+    const long span_k = ((long)n_blocks * n_tiles + n_wg - 1) / n_wg;  // tile units per workgroup of a stream-K plan
+    bool weighted = false;
+    if (any_thin && n_blocks <= 64) {
+      const double makespan = split_by_cost(cost, n_blocks, n_tiles, n_wg, sl);
+      weighted = streamk_env ? streamk_env[0] != '1' : makespan <= (double)span_k * 1.03 || !wgrad9_fits(n_tiles);
+    }
+    if (!weighted) {
+      const long q = n_wg / n_blocks, r = n_wg % n_blocks, worst = (n_tiles + q - 1) / q;
       for (int b = 0; b < n_blocks; ++b) {
-        const double tb = cost[b] * (double)((n_tiles + sl[b] - 1) / sl[b]);
-        if (tb > wt && sl[b] < n_tiles) wt = tb, worst = b;
+        const long v = q + (b < r ? 1 : 0);
+        sl[b] = (int)(v > n_tiles ? n_tiles : v);
       }
-      if (wt < 0) break;
-      ++sl[worst];
+      // stream-K only where the 4-wave kernel will run it: the r02 kernel takes equal slices only
+      const bool streamk = streamk_env ? streamk_env[0] == '1' : span_k >= 8 && worst * 100 > span_k * 103;
+      if (streamk && wgrad9_fits(n_tiles)) {
+        for (int b = 0; b < n_blocks; ++b) sl[b] = (int)((((long)(b + 1) * n_tiles - 1) / span_k) - (((long)b * n_tiles) / span_k) + 1);
+        span = span_k;
+      }
     }
   }
+  blocks[kWgSpan] = (int32_t)span;
+  int first = 0;
   for (int b = 0; b < n_blocks; ++b) {
     int32_t* t = blocks + kWgTableInts * b;
     const int nr = t[1] + t[3], nc = t[5] + t[7];
     SR_REQUIRE(t[1] >= 1 && t[3] >= 0 && nr <= 16 && t[5] >= 0 && t[7] >= 0 && nc <= 16,
                "sr_wgrad_plan: block %d has %d row / %d column fragments (1..16 / 0..16)", b, nr, nc);
-    const long mine = weighted ? sl[b] : per_block;
-    t[kWgSlices] = (int)mine, t[kWgFirstSlice] = first, first += (int)mine;
+    t[kWgSlices] = sl[b], t[kWgFirstSlice] = first, first += sl[b];
   }
   *n_slices = first;
   return 0;

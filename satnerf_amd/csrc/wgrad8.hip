@@ -265,11 +265,13 @@ __global__ void __launch_bounds__(1024) wgrad8_kernel(const Wgrad8Params prm) {
 }  // namespace sr
 
 namespace sr {
-int launch_wgrad8f(const uint4* dpre, const uint4* acts, const int* blocks, const int* loads, float* partial, long n_tiles, int n_blocks,
-                   int ak, int auxs, int dk, int n_slices, hipStream_t st);  // wgrad8f.hip
 int launch_wgrad9(const uint4* dpre, const uint4* acts, const uint4* emax, const int* blocks, const int* loads, float* partial, long n_tiles,
                   int n_blocks, int ak, int dk, int load_ints, int n_slices, int span, hipStream_t st);  // wgrad9.hip
-bool wgrad9_fits(long n_tiles, int ak, int dk);
+
+bool wgrad_v1() {
+  static const bool v1 = [] { const char* e = getenv("SATNERF_WGRAD_V1"); return e && e[0] == '1'; }();
+  return v1;
+}
 }
 using namespace sr;
 
@@ -290,16 +292,11 @@ extern "C" int sr_satnerf_wgrad8(int feat, int tau, int64_t n_points, const uint
   p.ak = (int)(sr_act_elems_per_tile(feat, SR_FMT8) / 512) - (2 - p.auxs);  // the size query assumes the 2-step aux layout
   p.dk = (int)(sr_dpre_elems_per_tile(feat, SR_FMT8) / 512);
   // default: the 4-wave kernel with 128 x 128 register tiles and the generated slice loop (wgrad9.hip), either width.  SATNERF_WGRAD_V1=1
-  // keeps the r02 kernel below (A/B; it also takes the workspaces beyond the 32-bit offsets of the new one); SATNERF_WGRAD_V2=1 the r03
-  // fat-wave experiment (wgrad8f.hip, width 256).
-  static const bool v1 = [] { const char* e = getenv("SATNERF_WGRAD_V1"); return e && e[0] == '1'; }();
-  static const bool v2 = [] { const char* e = getenv("SATNERF_WGRAD_V2"); return e && e[0] == '1'; }();
-  if (!v1 && !v2 && wgrad9_fits(p.n_tiles, p.ak, p.dk))
+  // keeps the r02 kernel below (A/B; it also takes the workspaces beyond the 32-bit offsets of the new one, mlp_layout.h)
+  if (!wgrad_v1() && wgrad9_fits(p.n_tiles, p.ak, p.dk))
     return launch_wgrad9(p.dpre, p.acts, p.dpre + sr::ws_tiles(n_points) * p.dk * 64 /* the exponent maxima behind the last tile */, blocks, loads,
                          partial, p.n_tiles, n_blocks, p.ak, p.dk, kWg8LoadInts, n_slices, plan_span, (hipStream_t)stream);
-  SR_REQUIRE(plan_span == 0, "sr_satnerf_wgrad8: a stream-K plan (span %d) needs the 4-wave kernel: plan with SATNERF_WGRAD_STREAMK=0 for the r02 / r03 kernels", plan_span);
-  if (feat == 256 && v2)
-    return launch_wgrad8f(p.dpre, p.acts, blocks, loads, partial, p.n_tiles, n_blocks, p.ak, p.auxs, p.dk, n_slices, (hipStream_t)stream);
+  SR_REQUIRE(plan_span == 0, "sr_satnerf_wgrad8: a stream-K plan (span %d) needs the 4-wave kernel: plan with SATNERF_WGRAD_STREAMK=0 for the r02 kernel", plan_span);
   const size_t lds = (size_t)kSlots8 * kSlot8Bytes;
   if (!ensure_dynamic_lds((const void*)wgrad8_kernel, lds)) return 1;
   hipLaunchKernelGGL(wgrad8_kernel, dim3(n_slices), dim3(1024), lds, (hipStream_t)stream, p);

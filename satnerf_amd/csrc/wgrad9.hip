@@ -498,12 +498,6 @@ __global__ void __launch_bounds__(256) wgrad9_kernel(const Wgrad9Params prm) {
   }  // next segment of a stream-K span
 }
 
-// the 4-wave kernel reads both workspaces through 32-bit per-lane offsets
-bool wgrad9_fits(long n_tiles, int ak, int dk) {
-  const long big = ak > dk ? ak : dk;
-  return n_tiles * big * 1024l < (1l << 32);
-}
-
 int launch_wgrad9(const uint4* dpre, const uint4* acts, const uint4* emax, const int* blocks, const int* loads, float* partial, long n_tiles,
                   int n_blocks, int ak, int dk, int load_ints, int n_slices, int span, hipStream_t st) {
   Wgrad9Params p;

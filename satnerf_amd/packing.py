@@ -443,7 +443,7 @@ def backward_maps(feat=256, tau=4):
 # csrc/mlp_layout.h (SR_FMT8): logical 16-bit fragment f of a workspace -> (unit, codec[, scale unit, scale byte]).
 SRC_DPRE, SRC_ACTS = 1, 2
 RAW16, PHASE8, MX8 = 0, 1, 2
-WG8_OLD_INTS = 20          # load table of the 16- / 8-wave kernels (wgrad8.hip, wgrad8f.hip)
+WG8_OLD_INTS = 20          # load table of the 16-wave kernel (wgrad8.hip)
 WG9_DUTY_INTS = 4 * 5 * 4  # duty table of the 4-wave kernel (wgrad9.hip): 4 waves x 5 duties x (source, unit, LDS fragment, scale)
 WG9_SCAN_INTS = 8          # ... + the exponent group (byte of an entry of the dX kernel's table of exponent maxima) of each of the block's 8 row pairs; -1 = none
 EMAX_FEATS, EMAX_RAW = 14, 15   # ... bytes 0..13 = the dpre scale groups (mlp_layout.h), 14 = the saved feats (columns of the MX8 blocks), 15 = the bf16 rows d_sigma_pre / d_head

@@ -54,6 +54,12 @@ def test_version_and_stream_geometry(handle):
     assert handle.sr_act_elems_per_tile(512, 8) == packing.act8_units(2, 512) * 512  # 512 wide: 8-bit workspaces only
     assert handle.sr_dpre_elems_per_tile(512, 8) == packing.dpre8_units(512) * 512 and handle.sr_act_elems_per_tile(512, 16) == -1
     assert handle.sr_act_elems_per_tile(256, 4) == -1 and handle.sr_wgrad8_load_ints() == packing.WG8_LOAD_INTS
+    # sr_wgrad_plan checks the 4-wave weight-gradient kernel's 32-bit offsets for kWg9PlanUnits 1-KiB units per tile: a bound on both 8-bit
+    # workspaces at either width, or it would plan stream-K for a workspace the launcher hands to the r02 kernel
+    layout = open(os.path.join(REPO, "satnerf_amd", "csrc", "mlp_layout.h")).read()
+    plan_units = int(re.search(r"constexpr int kWg9PlanUnits = (\d+);", layout).group(1))
+    for feat in (256, 512):
+        assert handle.sr_act_elems_per_tile(feat, 8) // 512 <= plan_units and handle.sr_dpre_elems_per_tile(feat, 8) // 512 <= plan_units
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

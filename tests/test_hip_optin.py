@@ -1,6 +1,6 @@
 """The kernels behind the A/B switches stay correct: SATNERF_FWD_V1=1 (the hipcc-scheduled forward kernels of mlp_fwd.inc instead of the
-generated cores -- also the fallback when a workspace exceeds the generated streams' 32-bit offsets) and SATNERF_WGRAD_V2=1 (the
-fat-wave weight-gradient kernel wgrad8f.hip), r06: SATNERF_WGRAD_THIN=0 / SATNERF_WGRAD_NORAW=0.  The switches are read once per process, so each case runs the relevant reference-golden
+generated cores -- also the fallback when a workspace exceeds the generated streams' 32-bit offsets), r06: SATNERF_WGRAD_THIN=0 /
+SATNERF_WGRAD_NORAW=0.  The switches are read once per process, so each case runs the relevant reference-golden
 tests in a child interpreter with the variable set."""
 import os
 import subprocess
@@ -29,11 +29,6 @@ def test_hipcc_scheduled_forward_kernels_match_the_goldens():
 @pytest.mark.gpu
 def test_hipcc_scheduled_training_forward_matches_the_gradient_goldens():
     _run({"SATNERF_FWD_V1": "1"}, "test_hip_backward.py", "gradients_match_reference_golden")
-
-
-@pytest.mark.gpu
-def test_fat_wave_weight_gradient_kernel_matches_the_gradient_goldens():
-    _run({"SATNERF_WGRAD_V2": "1"}, "test_hip_backward.py", "gradients_match_reference_golden or direct_step_matches_autograd")
 
 
 @pytest.mark.gpu

@@ -19,10 +19,6 @@ ws_tiles = _lib.lib().sr_workspace_tiles(n_points)
 dpre = torch.randint(0, 30000, (_lib.lib().sr_dpre_workspace_elems(n_points, 256, 8),), dtype=torch.int16, device=dev)
 dpre[ws_tiles * dp_e:].view(torch.uint8).fill_(120)
 n_wgs = [int(a) for a in sys.argv[2:]] or [0]
-dbg = None
-if os.environ.get("AB_TIMING"):  # kernel built with -DSR_W8_TIMING: per-wave s_memtime stamps of workgroup 0
-    dbg = torch.zeros(16 * 32 * 8, dtype=torch.int64, device=dev)
-    os.environ["SR_W8_DBG"] = str(dbg.data_ptr())
 dbg9 = None
 if os.environ.get("AB_TIMING9"):  # wgrad9.hip built with -DSR_W9_TIMING: per workgroup (shader cycles, 100-MHz ticks, tiles)
     dbg9 = torch.zeros(8 * 1024, dtype=torch.int64, device=dev)
@@ -47,18 +43,6 @@ for n_wg in n_wgs:
         e1.record(); torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1) / 20)
     print(f"{os.path.basename(os.environ.get('SATRENDER_LIB', 'default')):28s} points={n_points} n_wg={n_wg} slices={n_slices} {best*1e3:8.1f} us")
-
-if dbg is not None:
-    torch.cuda.synchronize()
-    d = dbg.cpu().view(16, 32, 8)
-    names = ["start", "issued", "tile", "vmwait", "barrier"]
-    for w in (0, 1, 3, 4, 5, 7):
-        print(f"wave {w}: per-iteration deltas (shader cycles) iterations 8..15")
-        for i in range(8, 16):
-            row = d[w, i]
-            deltas = [int(row[k] - row[k - 1]) for k in range(1, 5)]
-            nxt = int(d[w, i + 1, 0] - row[0])
-            print(f"  it {i:2d}: " + " ".join(f"{n}={v:5d}" for n, v in zip(names[1:], deltas)) + f"  | iter={nxt}")
 
 if dbg9 is not None:
     torch.cuda.synchronize()
