@@ -489,10 +489,11 @@ def wgrad_plan(blocks, n_points, n_wg=0, fmt=16):
     return ent[0], ent[1], ent[3]
 
 
-def wgrad_partials(feat, tau, n_points, dpre, acts, blocks, fmt=16, loads=None):
+def wgrad_partials(feat, tau, n_points, dpre, acts, blocks, fmt=16, loads=None, n_wg=0):
     """Weight-gradient GEMMs only: returns (fp32 split-K slices, planned job table); reduce with grad_tail / unpack_grads.
-    ``fmt`` = format of both workspaces; the 8-bit kernel also needs the per-block load table ``loads`` (packing.wgrad8_loads)."""
-    plan, n_slices, span = wgrad_plan(blocks, n_points, fmt=fmt)
+    ``fmt`` = format of both workspaces; the 8-bit kernel also needs the per-block load table ``loads`` (packing.wgrad8_loads).
+    ``n_wg`` = workgroups the plan is made for (0: the device's CU count)."""
+    plan, n_slices, span = wgrad_plan(blocks, n_points, n_wg=n_wg, fmt=fmt)
     block_floats = 256 * 256 + 256 * 32  # csrc/mlp_layout.h kWgBlockFloats
     partial = _ws_empty(n_slices * block_floats, torch.float32, dpre.device, 3)
     ev = kernel_timer.span("wgrad") if kernel_timer is not None else None
