@@ -413,6 +413,32 @@ int sr_dsm_rasterize(const double* east, const double* north, const double* alt,
                      double resolution, int xsize, int ysize, int radius, double sigma, uint64_t* acc, float* dsm, float* weight,
                      void* stream);
 
+/* ---- DSM registration: dsmr.compute_shift / dsmr.apply_shift (dsmr.py:6-148,163-215), the XY + Z
+ * registration of sat_utils.dsm_pointwise_diff (sat_utils.py:172-177) --------------------------------------------------------------
+ * u (hu, wu) is the reference DSM (the ground truth), v (hv, wv) the secondary (the prediction): row-major DEVICE fp64 (exact
+ * widenings of fp32 rasters), shapes may differ, every side in 1..16384.  A pixel counts only when finite; reads outside v are NaN.
+ * sr_dsm_register_scratch: HOST only; bytes of caller-owned scratch sr_dsm_compute_shift needs, and the number of levels (1 + the
+ * halvings while min(h, w) of u > 100, recursive_ncc dsmr.py:121-135).
+ * sr_dsm_downsample2x: downsample2x_ (dsmr.py:17-48), out ((h+1)/2, (w+1)/2) fp64: cell (J, I) = the mean of the finite in-bounds
+ * pixels of the 2x2 window at (min(2J+1, h-1), min(2I+1, w-1)) (the reference's last write wins), summed in the order (j,i),
+ * (j+1,i), (j,i+1), (j+1,i+1), NaN if none; bitwise the reference's.  The kernel compute_shift uses for every level.
+ * sr_dsm_compute_shift: recursive_ncc with irange (1..16) and compute_shift's coefficients (dsmr.py:102-135,184-188).  At each level
+ * every shift (x, y) = start +- irange gets mean_std's two-pass fp64 statistics (dsmr.py:50-88) and ncc = xcorr / (sig_u sig_v);
+ * the first strict maximum scanning y outer, x inner wins and the next finer level starts at twice it.  Departure: a shift with
+ * no valid pair or zero variance (where the reference raises ZeroDivisionError) gets ncc NaN and is never chosen; a level without a
+ * finite ncc keeps its start.  Writes shift (2 DEVICE ints) = (dx, dy) and coef (8 DEVICE doubles) = {a, b, mu_u, mu_v, sig_u,
+ * sig_v, xcorr, count} at that shift, a = sig_u / sig_v if scaling else 1, b = mu_u - mu_v a; count 0 means no answer.  Optional
+ * (NULL to skip): ncc_levels (levels x (2 irange + 1)^2 DEVICE doubles, level 0 the finest, [y][x]) and start_levels (levels x 2
+ * DEVICE ints).  The running shift lives in scratch: no host synchronisation, capturable.  Partials are summed in a fixed order
+ * set by the shapes alone, so results are bitwise repeatable.
+ * sr_dsm_apply_shift: apply_shift_ (dsmr.py:138-148) over v's extent: out[j, i] = a v[j + dy, i + dx] + b in fp64 (NaN outside v),
+ * stored fp32 (hv, wv); (dx, dy) and (a, b) are read from the DEVICE shift / coef of sr_dsm_compute_shift. */
+int sr_dsm_register_scratch(int hu, int wu, int hv, int wv, int irange, int64_t* bytes, int* levels);
+int sr_dsm_downsample2x(const double* in, int h, int w, double* out, void* stream);
+int sr_dsm_compute_shift(const double* u, int hu, int wu, const double* v, int hv, int wv, int irange, int scaling, void* scratch,
+                         int64_t scratch_bytes, int* shift, double* coef, double* ncc_levels, int* start_levels, void* stream);
+int sr_dsm_apply_shift(const double* v, int hv, int wv, const int* shift, const double* coef, float* out, void* stream);
+
 /* ---- training-step kernels --------------------------------------------------------------
  * sr_satnerf_loss: metrics.SatNerfLoss for the coarse model (metrics.py:21-25,56-73): value = sum of
  * loss_parts[0 .. ceil(N/4)), and grad_scale * dLoss/d{rgb (N,3), weights (N,S), beta (N,S)} in g_*.

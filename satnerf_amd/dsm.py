@@ -1,9 +1,10 @@
-"""DSM extraction on the GPU: depth -> UTM point cloud -> rasterised DSM -> Z-registered DSM MAE.
+"""DSM extraction on the GPU: depth -> UTM point cloud -> rasterised DSM -> registered DSM MAE.
 
 The reference leaves the GPU here and calls pyproj / utm (``sat_utils.utm_from_latlon``), plyflatten
 (``SatelliteDataset.get_dsm_from_nerf_prediction``) and GDAL / rasterio (``sat_utils.dsm_pointwise_diff``).  This module keeps
 their names and argument order; geometry is fp64, the rasteriser is the HIP kernel of csrc/dsm.hip.  No file I/O: GeoTIFF reading
-and writing stay with the caller (``DSM.transform`` is the affine the reference writes).
+and writing stay with the caller (``DSM.transform`` is the affine the reference writes).  The reference's dsmr registration
+(``compute_shift`` / ``apply_shift``, numba on the CPU there) is the HIP search of csrc/dsm_register.hip.
 
 The rasteriser follows this project's own grid / splat convention (include/satrender.h, sr_dsm_rasterize).  plyflatten cannot be
 run here, so parity with it is not claimed.
@@ -140,13 +141,82 @@ def dsm_from_depth(rays, depth, center, scene_range, roi=None, resolution=0.5, r
     return DSM(dsm, weight, float(xoff), float(yoff), float(resolution), zone_str, None if roi is None else tuple(float(v) for v in roi))
 
 
-def dsm_mae(pred, gt, gt_mask=None):
-    """Z-only registration of ``sat_utils.dsm_pointwise_diff`` (sat_utils.py:162-171, the branch taken without dsmr): water cells
-    (mask class 9) become NaN in ``pred``, shift = nanmean(gt - pred), rdsm = pred + shift, err = rdsm - gt, mae = nanmean(|err|).
+def _raster(x, name):
+    """The (H, W) device raster of a :class:`DSM` or a tensor, as fp64 (an exact widening of fp32)."""
+    t = x.dsm if isinstance(x, DSM) else x
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError(f"{name} must be a DSM or a GPU tensor: satnerf_amd has no CPU path")
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"{name} must be a non-empty (H, W) raster, got shape {tuple(t.shape)}")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be floating point, got {t.dtype}")
+    return t.to(torch.float64).contiguous()
 
-    ``pred`` is a :class:`DSM` built with ``roi=`` or a (H, W) device tensor already on the ground truth's grid; ``gt`` (H, W) and
-    ``gt_mask`` (H, W) live on the same device.  No cropping (the reference's gdal.Translate) happens here.  Arithmetic is fp64.
-    Returns (mae, err, rdsm, shift): mae / shift as floats, err / rdsm as fp64 device tensors."""
+
+def _check_irange(irange):
+    if not (isinstance(irange, int) and 1 <= irange <= 16):
+        raise ValueError(f"irange must be an int in 1..16, got {irange!r}")
+
+
+def _coefs(out):
+    """(dx, dy, a, b) from sr_dsm_compute_shift's packed result, in one device-to-host copy."""
+    host = out.cpu()
+    coef = host[:8].view(torch.float64).tolist()
+    dx, dy = host[8:].view(torch.int32).tolist()
+    if coef[7] == 0:
+        raise ValueError("no valid (finite) pixel pair at the registered shift: the registration is undefined")
+    return dx, dy, coef[0], coef[1]
+
+
+def compute_shift(ref, sec, scaling=True, irange=5):
+    """``dsmr.compute_shift`` (dsmr.py:163-190) on the GPU: the integer shift (dx, dy) and the Z map z -> a z + b that register ``sec``
+    on ``ref`` by a coarse-to-fine NCC search (csrc/dsm_register.hip).  ``ref`` / ``sec`` are DSMs or (H, W)
+    device rasters of any float dtype; their shapes may differ.  a = sig_ref / sig_sec if ``scaling`` else 1, b = mu_ref - mu_sec a
+    at the shift.  Returns (dx, dy, a, b) as Python numbers after one device-to-host copy; raises ValueError when no finite pixel
+    pair exists at the chosen shift (where the reference raises ZeroDivisionError)."""
+    _check_irange(irange)
+    u, v = _raster(ref, "ref"), _raster(sec, "sec")
+    out, _, _ = ops.dsm_compute_shift(u, v, irange=irange, scaling=scaling)
+    return _coefs(out)
+
+
+def apply_shift(sec, dx=0, dy=0, a=1.0, b=0.0):
+    """``dsmr.apply_shift`` (dsmr.py:193-215) without file I/O: out[j, i] = a sec[j + dy, i + dx] + b over sec's extent, NaN where
+    the read falls outside sec, evaluated in fp64 and returned as an fp32 device tensor (the reference's raster dtype)."""
+    v = _raster(sec, "sec")
+    shift = torch.tensor([int(dx), int(dy)], dtype=torch.int32).to(v.device)
+    coef = torch.tensor([float(a), float(b)], dtype=torch.float64).to(v.device)
+    return ops.dsm_apply_shift(v, shift, coef)
+
+
+def dsm_mae(pred, gt, gt_mask=None, register="z"):
+    """The DSM MAE of ``sat_utils.dsm_pointwise_diff`` + ``np.nanmean(abs(err))``.  Water cells (mask class 9) become NaN in ``pred``
+    first.  ``pred`` is a :class:`DSM` built with ``roi=`` or a (H, W) device tensor already on the ground truth's grid; ``gt`` (H, W)
+    and ``gt_mask`` (H, W) live on the same device.  No cropping (the reference's gdal.Translate) happens here.
+
+    register="z" (default): the branch the reference takes without dsmr (sat_utils.py:162-171): shift = nanmean(gt - pred),
+    rdsm = pred + shift, err = rdsm - gt, all fp64.  Returns (mae, err, rdsm, shift): mae / shift as floats, err / rdsm as fp64
+    device tensors.
+
+    register="xyz": the dsmr branch, i.e. the metric the reference prints (sat_utils.py:172-177): (dx, dy, a, b) =
+    compute_shift(gt, pred, scaling=False), rdsm = apply_shift(pred, dx, dy, a, b) (fp32), err = rdsm - gt (fp32 for an fp32 gt),
+    mae = nanmean(|err|) (summed in fp64).  Returns (mae, err, rdsm, (dx, dy, a, b)); registration runs entirely on the device and
+    the result comes back in one copy."""
+    if register not in ("z", "xyz"):
+        raise ValueError(f"register must be 'z' or 'xyz', got {register!r}")
+    if isinstance(pred, DSM):
+        if pred.roi is None:
+            raise ValueError("pred was not built on the ROI grid: call dsm_from_depth(..., roi=...) (cropping is not implemented)")
+        pred = pred.dsm
+    for name, t in (("pred", pred), ("gt", gt), ("gt_mask", gt_mask)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f"{name} must be a GPU tensor: satnerf_amd has no CPU path")
+    if pred.shape != gt.shape or pred.dim() != 2:
+        raise ValueError(f"pred {tuple(pred.shape)} is not on the ground truth's (H, W) grid {tuple(gt.shape)}")
+    if gt_mask is not None and gt_mask.shape != gt.shape:
+        raise ValueError(f"gt_mask {tuple(gt_mask.shape)} does not match gt {tuple(gt.shape)}")
+    if register == "xyz":
+        return _dsm_mae_xyz(pred, gt, gt_mask)
     if isinstance(pred, DSM):
         if pred.roi is None:
             raise ValueError("pred was not built on the ROI grid: call dsm_from_depth(..., roi=...) (cropping is not implemented)")
@@ -166,6 +236,19 @@ def dsm_mae(pred, gt, gt_mask=None):
     err = rdsm - g
     mae = torch.nanmean(err.abs())
     return mae.item(), err, rdsm, shift.item()
+
+
+def _dsm_mae_xyz(pred, gt, gt_mask):
+    p = _raster(pred, "pred").clone()
+    g = gt.to(pred.device)
+    if gt_mask is not None:
+        p[gt_mask == 9] = float("nan")
+    out, _, _ = ops.dsm_compute_shift(_raster(g, "gt"), p, irange=5, scaling=False)
+    rdsm = ops.dsm_apply_shift(p, out[8:].view(torch.int32), out[:8].view(torch.float64))
+    err = rdsm.to(torch.promote_types(torch.float32, g.dtype)) - g
+    mae = torch.nanmean(err.abs().double())
+    transform = _coefs(out)  # raises if the registration is undefined
+    return mae.item(), err, rdsm, transform
 
 
 def render_dsm(models, rays, ts, args, center, scene_range, **dsm_kwargs):

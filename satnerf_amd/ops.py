@@ -750,3 +750,63 @@ def dsm_rasterize(east, north, alt, xoff, yoff, resolution, xsize, ysize, radius
     _lib.call("sr_dsm_rasterize", _p(east), _p(north), _p(alt), east.shape[0], float(xoff), float(yoff), float(resolution), int(xsize),
               int(ysize), int(radius), float(sigma), _p(acc), _p(dsm), _p(weight), _stream())
     return dsm, weight
+
+
+# ---- DSM registration (csrc/dsm_register.hip) --------------------------------------------------------------------------------------
+def _raster(t, name):
+    t = _chk(t, name, torch.float64)
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be an (H, W) raster, got shape {tuple(t.shape)}")
+    return t
+
+
+def dsm_register_plan(u_shape, v_shape, irange=5):
+    """(scratch bytes, levels) of sr_dsm_compute_shift for these shapes (host only)."""
+    nbytes, levels = C.c_int64(0), C.c_int(0)
+    _lib.call("sr_dsm_register_scratch", int(u_shape[0]), int(u_shape[1]), int(v_shape[0]), int(v_shape[1]), int(irange), C.byref(nbytes),
+              C.byref(levels))
+    return nbytes.value, levels.value
+
+
+def dsm_downsample2x(img):
+    """((H+1)//2, (W+1)//2) fp64 device tensor: the reference's downsample2x_ of an fp64 (H, W) device raster."""
+    img = _raster(img, "img")
+    out = torch.empty((img.shape[0] + 1) // 2, (img.shape[1] + 1) // 2, dtype=torch.float64, device=img.device)
+    _lib.call("sr_dsm_downsample2x", _p(img), img.shape[0], img.shape[1], _p(out), _stream())
+    return out
+
+
+def dsm_compute_shift(u, v, irange=5, scaling=True, out=None, scratch=None, maps=False):
+    """Enqueue sr_dsm_compute_shift on fp64 (H, W) device rasters u (reference) and v (secondary).  ``out`` is a (9,) int64 device
+    tensor (allocated if None): coef (8 fp64) in out[:8], shift (2 int32) in out[8]; ``scratch`` a uint8 device tensor of at least
+    dsm_register_plan's bytes.  With maps=True also returns the per-level NCC maps (levels, n, n) fp64 and starts (levels, 2) int32.
+    Returns (out, ncc, starts); nothing is read back."""
+    u, v = _raster(u, "u"), _raster(v, "v")
+    _same_device(v, "v")
+    nbytes, levels = dsm_register_plan(u.shape, v.shape, irange)
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=u.device)
+    elif not (scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= nbytes):
+        raise ValueError(f"scratch must be a contiguous device tensor of >= {nbytes} bytes")
+    out = torch.empty(9, dtype=torch.int64, device=u.device) if out is None else _chk(out, "out", torch.int64)
+    n = 2 * int(irange) + 1
+    ncc = torch.empty(levels, n, n, dtype=torch.float64, device=u.device) if maps else None
+    starts = torch.empty(levels, 2, dtype=torch.int32, device=u.device) if maps else None
+    _lib.call("sr_dsm_compute_shift", _p(u), u.shape[0], u.shape[1], _p(v), v.shape[0], v.shape[1], int(irange), int(bool(scaling)),
+              _p(scratch), scratch.numel() * scratch.element_size(), out[8:].data_ptr(), out[:8].data_ptr(), _p(ncc), _p(starts),
+              _stream())
+    return out, ncc, starts
+
+
+def dsm_apply_shift(v, shift, coef, out=None):
+    """(H, W) fp32 device tensor: a v[j + dy, i + dx] + b over v's extent, (dx, dy) / (a, b) read on the device from ``shift`` (2
+    int32) and ``coef`` (>= 2 fp64)."""
+    v = _raster(v, "v")
+    shift, coef = _chk(shift, "shift", torch.int32), _chk(coef, "coef", torch.float64)
+    if shift.numel() < 2 or coef.numel() < 2:
+        raise ValueError("shift needs 2 int32 and coef at least 2 fp64")
+    out = torch.empty(v.shape, dtype=torch.float32, device=v.device) if out is None else _chk(out, "out")
+    if out.shape != v.shape:
+        raise ValueError(f"out must be {tuple(v.shape)}")
+    _lib.call("sr_dsm_apply_shift", _p(v), v.shape[0], v.shape[1], _p(shift), _p(coef), _p(out), _stream())
+    return out

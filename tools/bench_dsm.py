@@ -1,5 +1,6 @@
-"""DSM extraction timings (HIP events): dsm_from_depth over side x side points at radius 1 / 2, its three stages, and render_dsm
-of a side x side image at BASELINE configs[4]'s chunking (8192 rays x 128 samples).  Usage: bench_dsm.py [side ...]"""
+"""DSM extraction timings (HIP events, median of 10): dsm_from_depth over side x side points at radius 1 / 2, its three stages, the
+XY + Z registration (compute_shift, and the whole dsm_mae(register="xyz")) of a side x side DSM pair, and render_dsm of a side x side
+image at BASELINE configs[4]'s chunking (8192 rays x 128 samples).  Usage: bench_dsm.py [--registration-only] [side ...]"""
 import os
 import sys
 
@@ -54,9 +55,44 @@ def timed(fn, reps=10):
     return float(np.median(t))
 
 
+def registration_pair(side, dx=13, dy=-11, dz=0.7):
+    """A side x side DSM pair (boxes on a slope, a few NaN blobs) with v[j + dy, i + dx] = u[j, i] + dz, fp32 on the device."""
+    rng = np.random.default_rng(side)
+    pad = 32
+    jj, ii = np.meshgrid(np.arange(side + 2 * pad), np.arange(side + 2 * pad), indexing="ij")
+    f = 20.0 + 0.05 * ii - 0.03 * jj
+    for _ in range(side * side // 1500):
+        bh, bw = rng.integers(6, 40, size=2)
+        y0, x0 = rng.integers(0, f.shape[0] - bh), rng.integers(0, f.shape[1] - bw)
+        f[y0:y0 + bh, x0:x0 + bw] += rng.uniform(4.0, 40.0)
+    u = f[pad:pad + side, pad:pad + side] + rng.normal(0, 0.05, (side, side))
+    v = f[pad - dy:pad - dy + side, pad - dx:pad - dx + side] + dz + rng.normal(0, 0.05, (side, side))
+    u[side // 4:side // 4 + 20, side // 3:side // 3 + 30] = np.nan
+    return torch.from_numpy(u.astype(np.float32)).to(dev), torch.from_numpy(v.astype(np.float32)).to(dev)
+
+
+def bench_registration(side):
+    u, v = registration_pair(side)
+    u64, v64 = u.double(), v.double()
+    nbytes, levels = ops.dsm_register_plan(u.shape, v.shape, 5)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(9, dtype=torch.int64, device=dev)
+    t_cs = timed(lambda: ops.dsm_compute_shift(u64, v64, irange=5, scaling=False, out=out, scratch=scratch))
+    t_mae = timed(lambda: dsm.dsm_mae(v, u, register="xyz"))  # includes the fp64 widening, the apply, the MAE and its readback
+    _, _, _, (dx, dy, _, b) = dsm.dsm_mae(v, u, register="xyz")
+    print(f"registration {side}x{side}, {levels} levels, irange 5: compute_shift {t_cs:.3f} ms (device only), "
+          f"dsm_mae(register='xyz') {t_mae:.3f} ms end to end; recovered ({dx}, {dy}), b = {b:.4f}", flush=True)
+
+
 def main():
-    sides = [int(s) for s in sys.argv[1:]] or [512, 2048]
+    argv = sys.argv[1:]
+    registration_only = "--registration-only" in argv
+    sides = [int(s) for s in argv if s != "--registration-only"] or [512, 2048]
     print("device:", torch.cuda.get_device_name(0))
+    for side in sides:
+        bench_registration(side)
+    if registration_only:
+        return
     for side in sides:
         rays, depth, center = nadir_rays(side)
         e, n, a, _ = ops.depth_to_utm(rays, depth, center, RANGE)
