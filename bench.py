@@ -2,6 +2,7 @@
 """Headline benchmark: rays/s of the Sat-NeRF rendering hot path on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 200 --warmup 50
+    python bench.py --gpus 1 --steps 200 --warmup 50 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload = BASELINE.json configs[1]: sat-nerf, fc_units 256, tau 4, 1024 rays x 64 samples PER GPU (weak scaling),
@@ -9,14 +10,17 @@ synthetic GPU-resident rays, reference init weights, noise_std 0,
 A step = one pass of the hot path over one ray batch:
   --phase train   : render_rays with grad + SatNerf loss + backward + gradient all-reduce + Adam      (the metric)
   --phase forward : render_rays under no_grad (the batched_inference path)
-Prints ONE JSON line (rank 0).  Timing discipline: the step is captured into a hipGraph and run PREWARM (50) untimed steps
-before the `--warmup` steps, so the line does not depend on the CLI warm-up to reach steady clocks; the timed region is K
-graph replays bracketed by barrier + synchronize.  `roofline` follows SURVEY.md 8(d): the bounding roofline of this path is
-MFMA, so `achieved` = algorithmic FLOPs (1,318,912 per point and pass) / the dominant kernel's launch time against the dense
-bf16 peak, `step_frac` = the same for the whole step (3 passes: forward, dX, dW); kernel times are HIP events around EAGER
-launches of the same step right after the timed region (a graph replay cannot be bracketed per kernel from the host) -- the
+Prints ONE JSON line (rank 0).  A plain run does what that line's headline needs and no more: set-up, warm-up, the timed steps,
+the --dump-outputs arrays when asked for, the line.  `--full` adds everything else the benchmark measures (below: the eager
+roofline leg, the sub-records, the CPU baseline, the timed all-reduce of an N > 1 run); --no-extras / --no-cpu-baseline trim it.
+Timing discipline: the step is captured into a hipGraph and run PREWARM (50) untimed steps before the `--warmup` steps, so the
+line does not depend on the CLI warm-up to reach steady clocks; the timed region is K graph replays bracketed by barrier +
+synchronize.  With --full, `roofline` follows SURVEY.md 8(d): the bounding roofline of this path is MFMA, so `achieved` =
+algorithmic FLOPs (1,318,912 per point and pass) / the dominant kernel's launch time against the dense bf16 peak, `step_frac` =
+the same for the whole step (3 passes: forward, dX, dW); kernel times are HIP events around EAGER launches of the same step
+right after the timed region (a graph replay cannot be bracketed per kernel from the host) -- the
 rocprofv3 averages of the same command are committed under profiles/; `hbm_gbps` / `traffic` (PMC bytes per launch, read from
-the committed profiles/*_train_pmc.csv named in `traffic_source`) are the secondary view.  At N=1 the line also carries
+the committed profiles/*_train_pmc.csv named in `traffic_source`) are the secondary view.  At N=1 a --full line also carries
 `forward` (render_rays under no_grad, the batched_inference path) and `parity_mode` (the same training step in bf16x3 with
 16-bit saved state: the arithmetic that meets the 1e-4 output bar) sub-records, and `cpu_baseline` (the CPU oracle, a port of
 the reference's PyTorch path, on the host cores for a bounded sample of the same workload).
@@ -109,8 +113,11 @@ def parse():
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--mode", default="bf16", choices=["bf16", "f16", "bf16x3"])
     ap.add_argument("--phase", default=None, choices=["train", "forward"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward / parity_mode sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the eager roofline leg, the sub-records (N = 1, train), the CPU "
+                         "baseline and (N > 1) the timed gradient all-reduce")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the forward / parity_mode sub-records")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --rays per GPU (the default, what the driver's N = 1, 2, 4, 8 curve measures); strong: --rays in total, rank r takes rays r::N")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -438,25 +445,27 @@ def main():
     comm = None
     if world > 1:
         # self-verification of the N > 1 line (nobody but the driver owns a multi-GPU node): every rank contributes a one, so the
-        # reduced value is the number of ranks the collective really spanned; then the step's own collective -- one all-reduce of the
-        # flat fp32 gradient (662,537 + 120 floats = 2.65 MB) -- timed alone with HIP events
+        # reduced value is the number of ranks the collective really spanned (whole-job rays/s counts them); --full: then the step's
+        # own collective -- one all-reduce of the flat fp32 gradient (662,537 + 120 floats = 2.65 MB) -- timed alone with HIP events
         import torch.distributed as dist
 
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
-        flat = torch.zeros(662537 + 120, device=dev)
-        for _ in range(5):
-            dist.all_reduce(flat)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            dist.all_reduce(flat)
-        e1.record()
-        torch.cuda.synchronize()
-        comm = {"rccl_ranks": int(round(ones.item())), "backend": dist.get_backend(), "allreduce_us": e0.elapsed_time(e1) / 20 * 1e3,
-                "allreduce_bytes": flat.numel() * 4}
-    dt, kernel_ms, fmt = measure(phase, a.mode, rays_rank, a.samples, a.steps, a.warmup, world, rank, dev, dump_dir=a.dump_outputs)
+        comm = {"rccl_ranks": int(round(ones.item())), "backend": dist.get_backend()}
+        if a.full:
+            flat = torch.zeros(662537 + 120, device=dev)
+            for _ in range(5):
+                dist.all_reduce(flat)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                dist.all_reduce(flat)
+            e1.record()
+            torch.cuda.synchronize()
+            comm.update(allreduce_us=e0.elapsed_time(e1) / 20 * 1e3, allreduce_bytes=flat.numel() * 4)
+    dt, kernel_ms, fmt = measure(phase, a.mode, rays_rank, a.samples, a.steps, a.warmup, world, rank, dev, want_kernels=a.full,
+                                 dump_dir=a.dump_outputs)
     host_enqueue_s = measure.host_enqueue_s
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -469,24 +478,6 @@ def main():
     value = rays_rank * world * a.steps / dt
     points = rays_rank * a.samples
     flop = points * FLOP_PER_POINT  # one pass (forward, dX or dW) over the batch
-    tiles = (points + 31) // 32
-    au, du = WS_UNITS.get(fmt, (0, 0))
-    ws_bytes = {"mlp_fwd": tiles * au * 1024 if phase == "train" else points * 40, "mlp_bwd": tiles * (au + du) * 1024,
-                "wgrad": tiles * (au + du) * 1024}
-    kernels = {k: {"ms": ms, "tflops": flop / (ms * 1e-3) / 1e12, "flop": flop, "workspace_bytes": ws_bytes[k],
-                   "workspace_gbps": ws_bytes[k] / (ms * 1e-3) / 1e9} for k, ms in kernel_ms.items()}
-    dom = max(kernels, key=lambda k: kernels[k]["ms"])
-    passes = 3 if phase == "train" else 1
-    traffic = pmc_traffic(dom) if phase == "train" and a.mode == "bf16" and rays_rank == 1024 and a.samples == 64 else None
-    busy = {k: pmc_mfma_busy(k) for k in kernels} if phase == "train" and a.mode == "bf16" and rays_rank == 1024 and a.samples == 64 else {}
-    roof = {"bound": "mfma", "achieved": kernels[dom]["tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": kernels[dom]["tflops"] / MFMA_PEAK_TFLOPS, "kernel": KERNEL_NAMES[dom], "kernel_ms": kernels[dom]["ms"],
-            "mfma_busy": (busy.get(dom) or {}).get("frac"), "mfma_busy_all": {k: v for k, v in busy.items() if v},
-            "algorithmic_flop_per_launch": flop,
-            "step_achieved": passes * flop / (ms_step * 1e-3) / 1e12, "step_frac": passes * flop / (ms_step * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS,
-            "traffic": traffic, "traffic_source": PMC_FILE if traffic is not None else None,
-            "hbm_gbps": None if traffic is None else traffic / (kernels[dom]["ms"] * 1e-3) / 1e9, "hbm_peak_gbps": HBM_PEAK_GBPS,
-            "timing": "HIP events around eager launches of the same step, right after the timed region", "all_kernels": kernels}
     out = {
         "metric": "training rays/sec (64 samples/ray)" if phase == "train" else "inference rays/sec (64 samples/ray, render_rays no_grad)",
         "value": value, "unit": "rays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step,
@@ -501,15 +492,34 @@ def main():
                                + (", rays = consecutive chunks of the HBM-resident bank (one kernel per step)" if phase == "forward" else ""),
                    "rays_per_gpu": rays_rank, "global_batch": rays_rank * world,
                    "n_samples": a.samples, "parallelism": f"dp{world}"},
-        "roofline": roof,
     }
+    if a.full:
+        # the eager leg's kernel times against the MFMA roofline
+        passes = 3 if phase == "train" else 1
+        tiles = (points + 31) // 32
+        au, du = WS_UNITS.get(fmt, (0, 0))
+        ws_bytes = {"mlp_fwd": tiles * au * 1024 if phase == "train" else points * 40, "mlp_bwd": tiles * (au + du) * 1024,
+                    "wgrad": tiles * (au + du) * 1024}
+        kernels = {k: {"ms": ms, "tflops": flop / (ms * 1e-3) / 1e12, "flop": flop, "workspace_bytes": ws_bytes[k],
+                       "workspace_gbps": ws_bytes[k] / (ms * 1e-3) / 1e9} for k, ms in kernel_ms.items()}
+        dom = max(kernels, key=lambda k: kernels[k]["ms"])
+        traffic = pmc_traffic(dom) if phase == "train" and a.mode == "bf16" and rays_rank == 1024 and a.samples == 64 else None
+        busy = {k: pmc_mfma_busy(k) for k in kernels} if phase == "train" and a.mode == "bf16" and rays_rank == 1024 and a.samples == 64 else {}
+        out["roofline"] = {"bound": "mfma", "achieved": kernels[dom]["tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                           "frac": kernels[dom]["tflops"] / MFMA_PEAK_TFLOPS, "kernel": KERNEL_NAMES[dom], "kernel_ms": kernels[dom]["ms"],
+                           "mfma_busy": (busy.get(dom) or {}).get("frac"), "mfma_busy_all": {k: v for k, v in busy.items() if v},
+                           "algorithmic_flop_per_launch": flop,
+                           "step_achieved": passes * flop / (ms_step * 1e-3) / 1e12, "step_frac": passes * flop / (ms_step * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS,
+                           "traffic": traffic, "traffic_source": PMC_FILE if traffic is not None else None,
+                           "hbm_gbps": None if traffic is None else traffic / (kernels[dom]["ms"] * 1e-3) / 1e9, "hbm_peak_gbps": HBM_PEAK_GBPS,
+                           "timing": "HIP events around eager launches of the same step, right after the timed region", "all_kernels": kernels}
     if a.dump_outputs:
         out["dumped"] = measure.dumped  # (step = the dumped step's index in the leg, counting from 1)
     if phase == "train":
         out["schedule"] = measure.schedule      # StepLR + SNerfLoss warm-up are part of the measured step (main.py:86-94,128-131)
     if comm is not None:
         out["comm"] = dict(comm, **(measure.collective if phase == "train" else {}))
-    if world == 1 and not a.no_extras and phase == "train":
+    if a.full and world == 1 and not a.no_extras and phase == "train":
         # driver-timed numbers for the other two claims: the >= 40 % forward kernel and the tolerance-passing arithmetic
         n_sub = max(100, min(a.steps, 200))  # (>= 40 ms windows behind the MIN_WARM_S warm-up)
         n_fwd = 2000  # (0.09-ms steps: a window of 170 ms; a 20-step one would mostly time the fences around it)
@@ -575,7 +585,7 @@ def main():
             out["parity_grade"] = {"metric": "training rays/sec, mlp_mode=bf16x3 with bwd_fmt=32 (outputs <= 1e-4 AND gradients <= 2e-4 of the reference; "
                                              "layer-by-layer path, eager autograd)", "value": a.rays * n_pg / gdt, "ms_per_step": gdt / n_pg * 1e3, "steps": n_pg,
                                    "saved_state_bits": gfmt}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(phase, a.rays, a.samples)
     print(json.dumps(out))
 

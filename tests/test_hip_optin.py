@@ -44,12 +44,13 @@ def test_full_streams_for_the_one_row_blocks_match_the_gradient_goldens():
 @pytest.mark.gpu
 def test_bench_contract_with_two_ranks_sharing_the_gpu():
     """bench.py's N > 1 path (per-rank bank shares, barrier + max over ranks, whole-job rays/s) launched as the driver launches it; the two
-    ranks share the one GPU through the gloo test hook (measurements use nccl = RCCL, one rank per GPU)."""
+    ranks share the one GPU through the gloo test hook (measurements use nccl = RCCL, one rank per GPU).  The weak-scaling run is a --full
+    one (roofline leg, timed all-reduce), the strong-scaling run a plain one (the headline only)."""
     import json
 
     env = dict(os.environ, SATNERF_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+                        "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -66,11 +67,12 @@ def test_bench_contract_with_two_ranks_sharing_the_gpu():
     assert c["update_repacks"] is True  # r06: the N > 1 step is the N = 1 step split at the collective (no sr_pack_all, one update launch)
     assert d["schedule"]["steps_per_epoch"] >= 1 and d["schedule"]["warming_up"] is False and d["schedule"]["epoch"] >= 2
     assert d["provenance"]["lib"].endswith("libsatrender.so") and d["config"]["global_batch"] == 2048
-    # strong scaling: the same global batch split over the ranks
+    # strong scaling: the same global batch split over the ranks; a plain line: the rank count, no roofline, no timed all-reduce
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29534", "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--scaling", "strong"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["scaling"] == "strong" and d["config"]["rays_per_gpu"] == 512 and d["config"]["global_batch"] == 1024
+    assert d["comm"]["rccl_ranks"] == 2 and "allreduce_us" not in d["comm"] and "roofline" not in d and "cpu_baseline" not in d
     assert abs(d["value"] - 1024 * 5 / (d["ms_per_step"] * 5e-3)) < 1e-3 * d["value"]

@@ -4,7 +4,7 @@
 set -u
 TAG=${1:-r04}; root=$(pwd); out=$root/gpurun_out/profiles_${TAG}; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $root/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-extras"
+B="python $root/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $out/train_stats -o t --output-format csv -- $B > $out/train_stats.log 2>&1
 rocprofv3 --kernel-trace --stats -d $out/fwd_stats -o t --output-format csv -- $B --phase forward > $out/fwd_stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16" "SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU SQ_INSTS_LDS" "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU"; do
@@ -13,10 +13,10 @@ for c in FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_
 done
 cd $root
 if [ "${FULL:-0}" = "1" ]; then
-python bench.py --steps 200 --warmup 50 > $out/bench_train.json 2> $out/bench_train.err
-python bench.py --steps 200 --warmup 50 --phase forward > $out/bench_forward.json 2> $out/bench_forward.err
-python bench.py --steps 100 --warmup 20 --phase forward --rays 4096 --no-cpu-baseline > $out/bench_forward_4096rays.json 2> /dev/null
-python bench.py --steps 100 --warmup 20 --mode bf16x3 --no-cpu-baseline > $out/bench_train_bf16x3.json 2> /dev/null
+python bench.py --full --steps 200 --warmup 50 > $out/bench_train.json 2> $out/bench_train.err
+python bench.py --full --steps 200 --warmup 50 --phase forward > $out/bench_forward.json 2> $out/bench_forward.err
+python bench.py --full --steps 100 --warmup 20 --phase forward --rays 4096 --no-cpu-baseline > $out/bench_forward_4096rays.json 2> /dev/null
+python bench.py --full --steps 100 --warmup 20 --mode bf16x3 --no-cpu-baseline > $out/bench_train_bf16x3.json 2> /dev/null
 python tools/bench_layer_path.py 512 > $out/layer_path_512.txt 2>&1
 fi
 TAG=$TAG python - <<'PY'

@@ -6,7 +6,7 @@
 set -u
 TAG=${1:-r05}; root=$(pwd); out=$root/gpurun_out/profiles_${TAG}; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $root/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-extras"
+B="python $root/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-extras"
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/train_stats -o t --output-format csv -- $B > $out/train_stats.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/fwd_stats -o t --output-format csv -- $B --phase forward > $out/fwd_stats.log 2>&1
 if [ "${W512:-1}" = "1" ]; then

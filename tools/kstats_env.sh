@@ -6,7 +6,7 @@ mkdir -p $root/gpurun_out/$out
 cd /tmp && export TMPDIR=/tmp
 for e in "$@"; do
   d=$root/gpurun_out/$out/$(echo $e | tr '= ' '__')
-  env $e timeout 300 rocprofv3 --kernel-trace --stats -d $d -o p --output-format csv -- python $root/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-extras > /dev/null 2>&1
+  env $e timeout 300 rocprofv3 --kernel-trace --stats -d $d -o p --output-format csv -- python $root/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-extras > /dev/null 2>&1
   f=$(find $d -name "*kernel_stats.csv" | head -1)
   echo "== $e"; python3 - "$f" <<'PY'
 import csv,sys
