@@ -439,6 +439,27 @@ int sr_dsm_compute_shift(const double* u, int hu, int wu, const double* v, int h
                          int64_t scratch_bytes, int* shift, double* coef, double* ncc_levels, int* start_levels, void* stream);
 int sr_dsm_apply_shift(const double* v, int hv, int wv, const int* shift, const double* coef, float* out, void* stream);
 
+/* ---- image metrics: metrics.mse / metrics.psnr / metrics.ssim (metrics.py:105-121), the PSNR and SSIM of
+ * eval_satnerf.py:288-290 and main.py:194-195 -----------------------------------------------------------------------------------------
+ * Both reductions accumulate in fp64 and write out (2 DEVICE doubles) = {sum, count}.  Each workgroup's partial goes to caller-owned
+ * scratch and a second launch adds the partials in a fixed order; the grid depends on the shapes alone, so results are bitwise
+ * repeatable.  No host synchronisation: capturable.
+ * sr_image_metrics_scratch: HOST only; bytes of scratch that both sr_image_sse over n elements and sr_ssim_sum over (planes, h, w) need
+ * (planes 0: the SSE alone).
+ * sr_image_sse: metrics.mse's sum (metrics.py:105-112): sum of (pred - gt)^2 over n fp32 DEVICE elements, the difference and square
+ * in fp64.  mask (optional, n / mask_div DEVICE bytes, n a multiple of mask_div): element i counts when mask[i / mask_div] != 0
+ * (mask_div 1: per element; the trailing size: a mask over the leading dimensions, as torch boolean indexing).  count = the
+ * elements used, so mse = sum / count (NaN when nothing is used).
+ * sr_ssim_sum: the sum of kornia 0.5.3's losses.ssim map (metrics.py:116-121, window 3, max_val 1) over `planes` contiguous fp32
+ * (h, w) planes of each image (NCHW, planes = B * C, 2 <= h, w): the 3x3 Gaussian (sigma 1.5) moments with reflect borders
+ * (-1 -> 1, h -> h - 2), sigma = f(x^2) - mu^2 etc., map = ((2 mu1 mu2 + C1)(2 sigma12 + C2)) / ((mu1^2 + mu2^2 + C1)(sigma1^2 +
+ * sigma2^2 + C2) + 1e-12), C1 = 0.01^2, C2 = 0.03^2, all in fp64.  count = planes * h * w, so ssim = sum / count. */
+int sr_image_metrics_scratch(int64_t n, int64_t planes, int h, int w, int64_t* bytes);
+int sr_image_sse(const float* pred, const float* gt, int64_t n, const uint8_t* mask, int64_t mask_div, void* scratch,
+                 int64_t scratch_bytes, double* out, void* stream);
+int sr_ssim_sum(const float* img1, const float* img2, int64_t planes, int h, int w, void* scratch, int64_t scratch_bytes, double* out,
+                void* stream);
+
 /* ---- training-step kernels --------------------------------------------------------------
  * sr_satnerf_loss: metrics.SatNerfLoss for the coarse model (metrics.py:21-25,56-73): value = sum of
  * loss_parts[0 .. ceil(N/4)), and grad_scale * dLoss/d{rgb (N,3), weights (N,S), beta (N,S)} in g_*.

@@ -810,3 +810,53 @@ def dsm_apply_shift(v, shift, coef, out=None):
         raise ValueError(f"out must be {tuple(v.shape)}")
     _lib.call("sr_dsm_apply_shift", _p(v), v.shape[0], v.shape[1], _p(shift), _p(coef), _p(out), _stream())
     return out
+
+
+# ---- image metrics (csrc/image_metrics.hip) ---------------------------------------------------------------------------------------
+def image_metrics_scratch(n=0, planes=0, h=0, w=0):
+    """Bytes of scratch sr_image_sse over n elements and sr_ssim_sum over (planes, h, w) need (host only)."""
+    nbytes = C.c_int64(0)
+    _lib.call("sr_image_metrics_scratch", int(n), int(planes), int(h), int(w), C.byref(nbytes))
+    return nbytes.value
+
+
+def _metric_scratch(scratch, nbytes, dev):
+    if scratch is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if not (scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= nbytes):
+        raise ValueError(f"scratch must be a contiguous device tensor of >= {nbytes} bytes")
+    _same_device(scratch, "scratch")
+    return scratch
+
+
+def image_sse(pred, gt, mask=None, mask_div=1, out=None, scratch=None):
+    """(2,) fp64 device tensor {sum of (pred - gt)^2, count} over contiguous fp32 device tensors of one shape; ``mask`` (optional, bool or
+    uint8, numel = pred.numel() / mask_div) selects element i by mask[i // mask_div].  Nothing is read back."""
+    pred, gt = _chk(pred, "pred"), _chk(gt, "gt")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    n = pred.numel()
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"mask must be bool or uint8 (got {mask.dtype})")
+        mask = _chk(mask, "mask", mask.dtype)
+        if int(mask_div) < 1 or mask.numel() * int(mask_div) != n:
+            raise ValueError(f"mask holds {mask.numel()} entries, which times mask_div {mask_div} is not the {n} elements")
+    out = torch.empty(2, dtype=torch.float64, device=pred.device) if out is None else _chk(out, "out", torch.float64)
+    scratch = _metric_scratch(scratch, image_metrics_scratch(n=n), pred.device)
+    _lib.call("sr_image_sse", _p(pred), _p(gt), n, _p(mask), int(mask_div), _p(scratch), scratch.numel() * scratch.element_size(), _p(out),
+              _stream())
+    return out
+
+
+def ssim_sum(img1, img2, out=None, scratch=None):
+    """(2,) fp64 device tensor {sum of the SSIM map (window 3), B*C*H*W} over two contiguous fp32 (B, C, H, W) device tensors.  Nothing
+    is read back."""
+    img1, img2 = _chk(img1, "img1"), _chk(img2, "img2")
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise ValueError(f"img1 / img2 must be two (B, C, H, W) tensors of one shape, got {tuple(img1.shape)} / {tuple(img2.shape)}")
+    b, c, h, w = img1.shape
+    out = torch.empty(2, dtype=torch.float64, device=img1.device) if out is None else _chk(out, "out", torch.float64)
+    scratch = _metric_scratch(scratch, image_metrics_scratch(planes=b * c, h=h, w=w), img1.device)
+    _lib.call("sr_ssim_sum", _p(img1), _p(img2), b * c, h, w, _p(scratch), scratch.numel() * scratch.element_size(), _p(out), _stream())
+    return out
