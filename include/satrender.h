@@ -385,6 +385,32 @@ int sr_latlonalt_from_depth(const float* rays, int ray_stride, const float* dept
 int sr_rpc_rays(const double* rpc, int width, int height, double min_alt, double max_alt, const double* center, double range,
                 double sun_elevation_deg, double sun_azimuth_deg, float* rays11, float* rays8, void* stream);
 
+/* ---- depth supervision from tie points: SatelliteDataset_depth (datasets/satellite_depth.py:51-129) ---------
+ * `rpc` = 90 HOST doubles as for sr_rpc_rays (the full-resolution camera); colrow = n (col, row) DEVICE fp64 pairs (the JSON's
+ * keypoints.2d_coordinates); pts3d = n_pts x 3 DEVICE fp64 ECEF tie points (pts3d.npy); pts3d_idx = n DEVICE int64 rows of pts3d
+ * (keypoints.pts3d_indices; an index outside 0..n_pts-1 yields NaN and is never scattered).  No host synchronisation: capturable.
+ * sr_rpc_rays_at: get_rays + normalize_rays + sun at the keypoints (satellite_depth.py:64-75; datasets/satellite.py:18-65,218-244):
+ * sr_rpc_rays' per-pixel arithmetic at arbitrary (col, row), rays11 (n, 11) fp32 DEVICE; `center` = 3 HOST doubles.
+ * sr_reprojection_errors: satellite_depth.py:116-122 -- sat_utils.ecef_to_latlon_custom of pts3d[idx], rpc.projection, and the fp64
+ * pixel distance to colrow, err (n,) fp32 DEVICE (the reference stores it in a float32 matrix).
+ * sr_keypoint_weights_scratch: HOST only; bytes of caller-owned scratch sr_keypoint_weights needs for n_pts points and n_cams cameras.
+ * sr_keypoint_weights: satellite_depth.py:123-129 over all n observations of the dataset: cam (n,) DEVICE int64 = the image of each
+ * observation (0..n_cams-1), err = the sr_reprojection_errors of all of them.  Per (point, camera) the observation with the largest
+ * index wins (numpy's assignment keeps the last), e (n_pts,) fp32 DEVICE = its errors summed over cameras in camera order, e_mean (1
+ * fp32 DEVICE) = the mean of e over all n_pts points (unobserved points count with 0), w (n_pts,) fp32 DEVICE = exp(-(e / e_mean)^2).
+ * Sums accumulate in fp64 and are rounded to fp32 once (the reference sums in fp32); partials in a fixed order: bitwise repeatable.
+ * sr_tie_point_depths: satellite_depth.py:77-91 -- depths (n, 2) fp32 DEVICE = [|(fp32(pts3d[idx]) - center) / range - origin|, w[idx]]
+ * in fp32, origin = columns 0..2 of rays11 (sr_rpc_rays_at's output); w (n_pts DEVICE floats) may be NULL (column 1 = 0). */
+int sr_rpc_rays_at(const double* rpc, const double* colrow, int64_t n, double min_alt, double max_alt, const double* center, double range,
+                   double sun_elevation_deg, double sun_azimuth_deg, float* rays11, void* stream);
+int sr_reprojection_errors(const double* rpc, const double* colrow, const int64_t* pts3d_idx, int64_t n, const double* pts3d,
+                           int64_t n_pts, float* err, void* stream);
+int sr_keypoint_weights_scratch(int64_t n_pts, int n_cams, int64_t* bytes);
+int sr_keypoint_weights(const int64_t* pts3d_idx, const int64_t* cam, const float* err, int64_t n, int64_t n_pts, int n_cams,
+                        void* scratch, int64_t scratch_bytes, float* e, float* w, float* e_mean, void* stream);
+int sr_tie_point_depths(const float* rays11, const double* pts3d, const int64_t* pts3d_idx, int64_t n, int64_t n_pts,
+                        const double* center, double range, const float* w, float* depths, void* stream);
+
 /* ---- DSM extraction: SatelliteDataset.get_dsm_from_nerf_prediction (datasets/satellite.py:277-338) -------------
  * sr_utm_zone: utm.latlon_to_zone_number + utm.latitude_to_zone_letter as sat_utils.utm_from_latlon uses them (sat_utils.py:105-106),
  * HOST only: lon normalised to [-180, 180), Norway (zone 32) and Svalbard (31/33/35/37) exceptions, letter = ASCII code of

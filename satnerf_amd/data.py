@@ -158,6 +158,111 @@ def rays_from_rpc(rpc, height, width, min_alt, max_alt, center, scene_range, sun
     return rays
 
 
+def read_scene_loc(root_dir):
+    """(center (3,) fp32 tensor, scene_range float) from ``root_dir/scene.loc`` as ``SatelliteDataset.__init__`` loads them
+    (datasets/satellite.py:108-110): both rounded to fp32 (``scene_range`` is the fp32 maximum of the three scales, returned as a
+    Python float of that value).  The file is required: the reference writes it in ``init_scaling_params``, which cannot serialise
+    its own float32 values, and this project does not create it."""
+    import json
+    import os
+
+    path = os.path.join(root_dir, "scene.loc")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"Could not find {path}: the scene's normalisation (X/Y/Z_offset and X/Y/Z_scale of the ECEF bounds) is "
+                                "required; write it with the scene's dataset tools (it is not computed here)")
+    with open(path) as f:
+        d = json.load(f)
+    center = torch.tensor([float(d["X_offset"]), float(d["Y_offset"]), float(d["Z_offset"])])
+    scene_range = torch.max(torch.tensor([float(d["X_scale"]), float(d["Y_scale"]), float(d["Z_scale"])]))
+    return center, float(scene_range)
+
+
+def depth_supervision_from_keypoints(images, tie_points, center, scene_range, device="cuda", return_point_weights=False, names=None):
+    """The depth-supervision data of ``SatelliteDataset_depth.load_depth_data`` (datasets/satellite_depth.py:51-129), on the GPU.
+
+    ``images``: the per-image JSON dicts of the training split, in order (image t gets ``ts`` = t), each with ``rpc`` (rpcm format,
+    full resolution), ``keypoints`` {``2d_coordinates`` (K, 2) = (col, row), ``pts3d_indices`` (K,)}, ``min_alt``, ``max_alt``,
+    ``sun_elevation``, ``sun_azimuth``; ``tie_points``: (n_pts, 3) fp64 ECEF (pts3d.npy); ``center`` / ``scene_range``: from
+    ``read_scene_loc``; ``names``: per-image labels for error messages (the JSON paths).  Returns (rays (N, 11), depths (N, 2) =
+    [target depth, keypoint weight], ts (N,) int64) on ``device``, ready for ``DepthBank``; with ``return_point_weights`` also the
+    per-tie-point error sums ``e`` and weights ``w`` (n_pts,).  The host only parses and uploads the tables once; every
+    per-observation step runs in HIP.  Departures: an image without keypoints adds no rays but counts as a
+    camera; indices outside pts3d and a zero or non-finite mean error raise ``ValueError``."""
+    import math
+
+    import numpy as np
+
+    from . import ops
+
+    pts = np.ascontiguousarray(np.asarray(tie_points, dtype=np.float64))
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError(f"tie_points must be (n_pts, 3) ECEF points with n_pts >= 1, got {pts.shape}")
+    n_pts, n_cams = pts.shape[0], len(images)
+    if n_cams < 1:
+        raise ValueError("no training images")
+    colrows, idxs, counts = [], [], []
+    for t, d in enumerate(images):
+        name = names[t] if names is not None else f"image {t}"
+        if "keypoints" not in d.keys():
+            raise ValueError("No 'keypoints' field was found in {}".format(name))
+        cr = np.asarray(d["keypoints"]["2d_coordinates"], dtype=np.float64).reshape(-1, 2)
+        ix = np.asarray(d["keypoints"]["pts3d_indices"], dtype=np.int64).reshape(-1)
+        if cr.shape[0] != ix.shape[0]:
+            raise ValueError(f"{name}: {cr.shape[0]} keypoints but {ix.shape[0]} pts3d_indices")
+        if ix.size and (ix.min() < 0 or ix.max() >= n_pts):
+            raise ValueError(f"{name}: pts3d_indices must lie in 0..{n_pts - 1} (got {ix.min()}..{ix.max()})")
+        colrows.append(cr), idxs.append(ix), counts.append(ix.size)
+    n = int(sum(counts))
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        colrow = torch.from_numpy(np.concatenate(colrows)).to(dev)
+        idx = torch.from_numpy(np.concatenate(idxs)).to(dev)
+        ts = torch.repeat_interleave(torch.arange(n_cams, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64)).to(dev)
+        pts3d = torch.from_numpy(pts).to(dev)
+        rays = torch.empty(n, 11, dtype=torch.float32, device=dev)
+        err = torch.empty(n, dtype=torch.float32, device=dev)
+        off = 0
+        for d, k in zip(images, counts):
+            if k:
+                sl = slice(off, off + k)
+                ops.rpc_rays_at(d["rpc"], colrow[sl], float(d["min_alt"]), float(d["max_alt"]), center, scene_range, float(d["sun_elevation"]),
+                                float(d["sun_azimuth"]), out=rays[sl])
+                ops.reprojection_errors(d["rpc"], colrow[sl], idx[sl], pts3d, out=err[sl])
+            off += k
+        e, w, e_mean = ops.keypoint_weights(idx, ts, err, n_pts, n_cams)
+        depths = ops.tie_point_depths(rays, pts3d, idx, center, scene_range, w=w)
+        em = e_mean.item()  # the one host synchronisation
+    if not (math.isfinite(em) and em > 0):
+        raise ValueError(f"the mean reprojection error over the tie points is {em}: the keypoint weights exp(-(e / e_mean)^2) are "
+                         "undefined (no observed tie point, or non-finite errors)")
+    return (rays, depths, ts, e, w) if return_point_weights else (rays, depths, ts)
+
+
+def load_depth_supervision(root_dir, device="cuda", return_point_weights=False):
+    """``SatelliteDataset_depth(root_dir, img_dir, split="train")``'s ``all_rays``, ``all_depths`` and ``all_ids`` (datasets/
+    satellite_depth.py:31-101) on the GPU, from ``scene.loc``, ``train.txt``, the training JSONs and ``pts3d.npy`` under
+    ``root_dir`` -- no images and no ``img_dir``.  Returns what ``depth_supervision_from_keypoints`` returns (ts = the image's line
+    in train.txt; blank lines are skipped)."""
+    import json
+    import os
+
+    import numpy as np
+
+    center, scene_range = read_scene_loc(root_dir)
+    with open(os.path.join(root_dir, "train.txt")) as f:
+        json_files = [os.path.join(root_dir, line) for line in f.read().split("\n") if line.strip()]
+    pts_path = root_dir + "/pts3d.npy"
+    if not os.path.exists(pts_path):
+        raise FileNotFoundError("Could not find {}".format(pts_path))
+    tie_points = np.load(pts_path)
+    images = []
+    for p in json_files:
+        with open(p) as f:
+            images.append(json.load(f))
+    return depth_supervision_from_keypoints(images, tie_points, center, scene_range, device=device,
+                                            return_point_weights=return_point_weights, names=json_files)
+
+
 def synthetic_rays(n_rays, seed=20240628, n_images=19, far_lo=0.5, far_hi=1.0):
     """Synthetic sat-nerf ray batch for benchmarks (no dataset ships offline): origins U[-1,1]^3, unit directions, near = 0
     (datasets/satellite.py:60), far U[far_lo, far_hi] (scene-normalised, :225-226), one sun direction per synthetic image id

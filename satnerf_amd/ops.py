@@ -393,6 +393,106 @@ def rpc_rays(rpc, width, height, min_alt, max_alt, center, scene_range, sun_elev
     return rays, cache
 
 
+def rpc_buffer(rpc):
+    """The 90 HOST doubles of an "rpcm"-format RPC dict in the C ABI's order (include/satrender.h, sr_rpc_rays)."""
+    vals = []
+    for k in RPC_KEYS:
+        c = [float(v) for v in rpc[k]]
+        if len(c) != 20:
+            raise ValueError(f"rpc[{k!r}] must hold the 20 RPC00B coefficients, got {len(c)}")
+        vals += c
+    vals += [float(rpc[k]) for k in RPC_SCALARS]
+    return (C.c_double * 90)(*vals)
+
+
+def _colrow(colrow):
+    colrow = _chk(colrow, "colrow", torch.float64)
+    if colrow.dim() != 2 or colrow.shape[1] != 2:
+        raise ValueError(f"colrow must be (n, 2) = (col, row) pairs, got {tuple(colrow.shape)}")
+    return colrow
+
+
+def _pts3d(pts3d):
+    pts3d = _chk(pts3d, "pts3d", torch.float64)
+    if pts3d.dim() != 2 or pts3d.shape[1] != 3:
+        raise ValueError(f"pts3d must be (n_pts, 3) ECEF points, got {tuple(pts3d.shape)}")
+    return pts3d
+
+
+def _index(idx, n, name="pts3d_idx"):
+    idx = _chk(idx, name, torch.int64)
+    if idx.dim() != 1 or idx.numel() != n:
+        raise ValueError(f"{name} must be ({n},), got {tuple(idx.shape)}")
+    return idx
+
+
+def rpc_rays_at(rpc, colrow, min_alt, max_alt, center, scene_range, sun_elevation_deg, sun_azimuth_deg, out=None):
+    """sr_rpc_rays_at: the (n, 11) fp32 normalised rays of one image at n (col, row) points (``colrow``: (n, 2) fp64 device tensor)."""
+    colrow = _colrow(colrow)
+    n = colrow.shape[0]
+    out = torch.empty(n, 11, dtype=torch.float32, device=colrow.device) if out is None else _chk(out, "out")
+    if tuple(out.shape) != (n, 11):
+        raise ValueError(f"out must be ({n}, 11), got {tuple(out.shape)}")
+    buf, ctr = rpc_buffer(rpc), (C.c_double * 3)(*[float(v) for v in center])
+    _lib.call("sr_rpc_rays_at", C.addressof(buf), _p(colrow), n, float(min_alt), float(max_alt), C.addressof(ctr), float(scene_range),
+              float(sun_elevation_deg), float(sun_azimuth_deg), _p(out), _stream())
+    return out
+
+
+def reprojection_errors(rpc, colrow, pts3d_idx, pts3d, out=None):
+    """sr_reprojection_errors: (n,) fp32 pixel distance between each keypoint and the RPC projection of its tie point."""
+    colrow, pts3d = _colrow(colrow), _pts3d(pts3d)
+    n = colrow.shape[0]
+    pts3d_idx = _index(pts3d_idx, n)
+    out = torch.empty(n, dtype=torch.float32, device=colrow.device) if out is None else _chk(out, "out")
+    if out.numel() != n:
+        raise ValueError(f"out must hold {n} floats")
+    buf = rpc_buffer(rpc)
+    _lib.call("sr_reprojection_errors", C.addressof(buf), _p(colrow), _p(pts3d_idx), n, _p(pts3d), pts3d.shape[0], _p(out), _stream())
+    return out
+
+
+def keypoint_weights_scratch(n_pts, n_cams):
+    """Bytes of scratch sr_keypoint_weights needs (host only)."""
+    nbytes = C.c_int64(0)
+    _lib.call("sr_keypoint_weights_scratch", int(n_pts), int(n_cams), C.byref(nbytes))
+    return nbytes.value
+
+
+def keypoint_weights(pts3d_idx, cam, err, n_pts, n_cams, scratch=None):
+    """sr_keypoint_weights over all observations: returns (e (n_pts,), w (n_pts,), e_mean (1,)) fp32 device tensors.  Nothing is
+    read back."""
+    err = _chk(err, "err")
+    n = err.numel()
+    pts3d_idx, cam = _index(pts3d_idx, n), _index(cam, n, "cam")
+    dev = err.device
+    scratch = _metric_scratch(scratch, keypoint_weights_scratch(n_pts, n_cams), dev)
+    e = torch.empty(int(n_pts), dtype=torch.float32, device=dev)
+    w = torch.empty_like(e)
+    e_mean = torch.empty(1, dtype=torch.float32, device=dev)
+    _lib.call("sr_keypoint_weights", _p(pts3d_idx), _p(cam), _p(err), n, int(n_pts), int(n_cams), _p(scratch),
+              scratch.numel() * scratch.element_size(), _p(e), _p(w), _p(e_mean), _stream())
+    return e, w, e_mean
+
+
+def tie_point_depths(rays, pts3d, pts3d_idx, center, scene_range, w=None, out=None):
+    """sr_tie_point_depths: (n, 2) fp32 [target depth, w[idx]] of the n rays (columns 0..2 = normalised origins)."""
+    rays, pts3d = _chk(rays, "rays"), _pts3d(pts3d)
+    if rays.dim() != 2 or rays.shape[1] != 11:
+        raise ValueError(f"rays must be (n, 11), got {tuple(rays.shape)}")
+    n = rays.shape[0]
+    pts3d_idx = _index(pts3d_idx, n)
+    if w is not None and (_chk(w, "w").numel() != pts3d.shape[0]):
+        raise ValueError(f"w must hold one weight per tie point ({pts3d.shape[0]})")
+    out = torch.empty(n, 2, dtype=torch.float32, device=rays.device) if out is None else _chk(out, "out")
+    if tuple(out.shape) != (n, 2):
+        raise ValueError(f"out must be ({n}, 2), got {tuple(out.shape)}")
+    ctr = (C.c_double * 3)(*[float(v) for v in center])
+    _lib.call("sr_tie_point_depths", _p(rays), _p(pts3d), _p(pts3d_idx), n, pts3d.shape[0], C.addressof(ctr), float(scene_range), _p(w),
+              _p(out), _stream())
+    return out
+
+
 def sample_pdf(bins, weights, u, eps=1e-5):
     n, nb = bins.shape
     _chk(bins, "bins"), _chk(weights, "weights"), _chk(u, "u")
