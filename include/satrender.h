@@ -411,6 +411,30 @@ int sr_keypoint_weights(const int64_t* pts3d_idx, const int64_t* cam, const floa
 int sr_tie_point_depths(const float* rays11, const double* pts3d, const int64_t* pts3d_idx, int64_t n, int64_t n_pts,
                         const double* center, double range, const float* w, float* depths, void* stream);
 
+/* ---- tie-point interpolation: study_depth_supervision.idw_interpolation (:64-103) and the
+ * scipy.ndimage.gaussian_filter(mode="reflect") of save_heatmap_of_reprojection_error (:18-61), the interpolation behind
+ * check_depth_supervision_points (:105-203) ------------------------------------------------------------------------------------
+ * sr_idw_grid_scratch: HOST only; bytes of caller-owned scratch sr_idw_interpolate needs for k points and n_neighbors (1..32,
+ * n_neighbors <= k <= 2^30).
+ * sr_idw_interpolate: pts2d = k DEVICE fp64 (col, row) pairs carrying z (k DEVICE fp32); queries = n_query DEVICE fp64 (col, row)
+ * pairs, or with query NULL every pixel (col i % width, row i / width) of the height x width raster (n_query ignored).  Per query the
+ * n_neighbors nearest points by fp64 d^2 = dx*dx + dy*dy, ties to the lower index (an exhaustive search's answer: a grid over the
+ * points, rings of cells until no unvisited cell can be nearer); out (DEVICE fp64) = z[nearest] when n_neighbors is 1 or the
+ * nearest distance is < 1e-10, else sum((1/d_i) / sum(1/d_j) z_i) in fp64 in increasing distance.  Optional (NULL to skip): nn_idx
+ * (n_query x n_neighbors DEVICE ints, the chosen indices in that order) and visited (n_query DEVICE ints, points examined).  Points
+ * must be finite: a non-finite one is never chosen, and a query with fewer than n_neighbors finite points gets NaN and index -1.  No
+ * float atomics, no host synchronisation; bitwise repeatable.
+ * sr_gaussian_filter_f64: scipy.ndimage.gaussian_filter(in, sigma) with mode "reflect" on a row-major h x w DEVICE fp64 raster (each
+ * side 1..65535): taps0 / taps1 = the 2 r + 1 DEVICE fp64 taps of axis 0 / 1 (scipy's _gaussian_kernel1d, symmetric, r <= 200), radius
+ * -1 leaves that axis as it is (sigma <= 1e-15).  Axis 0 first into tmp (h x w DEVICE fp64, needed only when both axes are
+ * filtered), then axis 1 into out; each output = x[i] w[0] + sum for k = r .. 1 of (x[i-k] + x[i+k]) w[k] in fp64 (correlate1d's
+ * order), indices outside the axis reflected (period 2n).  in, tmp and out must not overlap. */
+int sr_idw_grid_scratch(int64_t k, int n_neighbors, int64_t* bytes);
+int sr_idw_interpolate(const double* pts2d, const float* z, int64_t k, const double* query, int64_t n_query, int height, int width,
+                       int n_neighbors, void* scratch, int64_t scratch_bytes, double* out, int* nn_idx, int* visited, void* stream);
+int sr_gaussian_filter_f64(const double* in, int h, int w, const double* taps0, int radius0, const double* taps1, int radius1,
+                           double* tmp, double* out, void* stream);
+
 /* ---- DSM extraction: SatelliteDataset.get_dsm_from_nerf_prediction (datasets/satellite.py:277-338) -------------
  * sr_utm_zone: utm.latlon_to_zone_number + utm.latitude_to_zone_letter as sat_utils.utm_from_latlon uses them (sat_utils.py:105-106),
  * HOST only: lon normalised to [-180, 180), Norway (zone 32) and Svalbard (31/33/35/37) exceptions, letter = ASCII code of

@@ -111,6 +111,9 @@ SIGNATURES = {
     "sr_keypoint_weights_scratch": (_i, [_i64, _i, C.POINTER(_i64)]),
     "sr_keypoint_weights": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sr_tie_point_depths": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _d, _vp, _vp, _vp]),
+    "sr_idw_grid_scratch": (_i, [_i64, _i, C.POINTER(_i64)]),
+    "sr_idw_interpolate": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sr_gaussian_filter_f64": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "sr_utm_zone": (_i, [_d, _d, C.POINTER(_i), C.POINTER(_i)]),
     "sr_utm_from_latlon": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "sr_depth_to_utm": (_i, [_vp, _i, _vp, _i64, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp]),

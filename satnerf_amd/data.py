@@ -238,11 +238,9 @@ def depth_supervision_from_keypoints(images, tie_points, center, scene_range, de
     return (rays, depths, ts, e, w) if return_point_weights else (rays, depths, ts)
 
 
-def load_depth_supervision(root_dir, device="cuda", return_point_weights=False):
-    """``SatelliteDataset_depth(root_dir, img_dir, split="train")``'s ``all_rays``, ``all_depths`` and ``all_ids`` (datasets/
-    satellite_depth.py:31-101) on the GPU, from ``scene.loc``, ``train.txt``, the training JSONs and ``pts3d.npy`` under
-    ``root_dir`` -- no images and no ``img_dir``.  Returns what ``depth_supervision_from_keypoints`` returns (ts = the image's line
-    in train.txt; blank lines are skipped)."""
+def read_depth_dataset(root_dir):
+    """(images, tie_points, center, scene_range, json_files) of a dataset directory as ``SatelliteDataset_depth`` reads them
+    (datasets/satellite_depth.py:31-49): ``scene.loc``, the JSONs listed in ``train.txt`` (blank lines skipped) and ``pts3d.npy``."""
     import json
     import os
 
@@ -259,6 +257,15 @@ def load_depth_supervision(root_dir, device="cuda", return_point_weights=False):
     for p in json_files:
         with open(p) as f:
             images.append(json.load(f))
+    return images, tie_points, center, scene_range, json_files
+
+
+def load_depth_supervision(root_dir, device="cuda", return_point_weights=False):
+    """``SatelliteDataset_depth(root_dir, img_dir, split="train")``'s ``all_rays``, ``all_depths`` and ``all_ids`` (datasets/
+    satellite_depth.py:31-101) on the GPU, from ``scene.loc``, ``train.txt``, the training JSONs and ``pts3d.npy`` under
+    ``root_dir`` -- no images and no ``img_dir``.  Returns what ``depth_supervision_from_keypoints`` returns (ts = the image's line
+    in train.txt; blank lines are skipped)."""
+    images, tie_points, center, scene_range, json_files = read_depth_dataset(root_dir)
     return depth_supervision_from_keypoints(images, tie_points, center, scene_range, device=device,
                                             return_point_weights=return_point_weights, names=json_files)
 

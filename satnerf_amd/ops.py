@@ -912,6 +912,67 @@ def dsm_apply_shift(v, shift, coef, out=None):
     return out
 
 
+# ---- tie-point interpolation (csrc/tie_points.hip) --------------------------------------------------------------------------------
+def idw_grid_scratch(k, n_neighbors):
+    """Bytes of scratch sr_idw_interpolate needs for k points and n_neighbors (host only)."""
+    nbytes = C.c_int64(0)
+    _lib.call("sr_idw_grid_scratch", int(k), int(n_neighbors), C.byref(nbytes))
+    return nbytes.value
+
+
+def idw_interpolate(pts2d, z, n_neighbors, query=None, height=0, width=0, want_indices=False, want_visited=False, out=None, scratch=None):
+    """sr_idw_interpolate: (Q,) fp64 IDW of the n_neighbors nearest of the k points ``pts2d`` ((k, 2) fp64 (col, row)) carrying ``z`` ((k,)
+    fp32), at the (Q, 2) fp64 ``query`` points or, with query None, at every pixel of the height x width raster (Q = h w, row-major).
+    ``want_indices`` adds the (Q, n_neighbors) int32 chosen indices, ``want_visited`` the (Q,) int32 points each query examined (returned
+    in that order after the values).  Nothing is read back."""
+    pts2d, z = _chk(pts2d, "pts2d", torch.float64), _chk(z, "z")
+    if pts2d.dim() != 2 or pts2d.shape[1] != 2 or z.dim() != 1 or z.shape[0] != pts2d.shape[0]:
+        raise ValueError(f"pts2d must be (k, 2) and z (k,), got {tuple(pts2d.shape)} and {tuple(z.shape)}")
+    _same_device(z, "z")
+    k, n = pts2d.shape[0], int(n_neighbors)
+    if query is not None:
+        query = _chk(query, "query", torch.float64)
+        if query.dim() != 2 or query.shape[1] != 2:
+            raise ValueError(f"query must be (Q, 2) = (col, row) pairs, got {tuple(query.shape)}")
+        nq = query.shape[0]
+    else:
+        nq = int(height) * int(width)
+    dev = pts2d.device
+    scratch = _metric_scratch(scratch, idw_grid_scratch(k, n), dev)
+    out = torch.empty(nq, dtype=torch.float64, device=dev) if out is None else _chk(out, "out", torch.float64)
+    if out.numel() != nq:
+        raise ValueError(f"out must hold {nq} doubles")
+    idx = torch.empty(nq, n, dtype=torch.int32, device=dev) if want_indices else None
+    seen = torch.empty(nq, dtype=torch.int32, device=dev) if want_visited else None
+    _lib.call("sr_idw_interpolate", _p(pts2d), _p(z), k, _p(query), nq if query is not None else 0, int(height), int(width), n, _p(scratch),
+              scratch.numel() * scratch.element_size(), _p(out), _p(idx), _p(seen), _stream())
+    extra = [t for t in (idx, seen) if t is not None]
+    return (out, *extra) if extra else out
+
+
+def gaussian_filter_f64(image, taps0, taps1, out=None, tmp=None):
+    """sr_gaussian_filter_f64: the (h, w) fp64 device raster filtered along axis 0 with the 1-D fp64 device ``taps0`` (2 r + 1 values),
+    then along axis 1 with ``taps1``, reflect borders; None skips an axis.  Returns a new (h, w) fp64 tensor (or ``out``)."""
+    image = _chk(image, "image", torch.float64)
+    if image.dim() != 2:
+        raise ValueError(f"image must be (h, w), got {tuple(image.shape)}")
+    radii = []
+    for t, name in ((taps0, "taps0"), (taps1, "taps1")):
+        if t is not None and (_chk(t, name, torch.float64).dim() != 1 or t.numel() % 2 != 1):
+            raise ValueError(f"{name} must hold 2 r + 1 taps")
+        radii.append(-1 if t is None else t.numel() // 2)
+    out = torch.empty_like(image) if out is None else _chk(out, "out", torch.float64)
+    if out.shape != image.shape:
+        raise ValueError(f"out must be {tuple(image.shape)}")
+    if taps0 is not None and taps1 is not None:
+        tmp = torch.empty_like(image) if tmp is None else _chk(tmp, "tmp", torch.float64)
+        if tmp.shape != image.shape:
+            raise ValueError(f"tmp must be {tuple(image.shape)}")
+    _lib.call("sr_gaussian_filter_f64", _p(image), image.shape[0], image.shape[1], _p(taps0), radii[0], _p(taps1), radii[1], _p(tmp), _p(out),
+              _stream())
+    return out
+
+
 # ---- image metrics (csrc/image_metrics.hip) ---------------------------------------------------------------------------------------
 def image_metrics_scratch(n=0, planes=0, h=0, w=0):
     """Bytes of scratch sr_image_sse over n elements and sr_ssim_sum over (planes, h, w) need (host only)."""
