@@ -73,6 +73,11 @@ class Operand:
         n = 256.0 if self.codec == "ph8" else 65535.0
         return torch.sin(2 * math.pi * self.u.to(torch.float64) / n)
 
+    def revolutions(self):
+        """Phase codecs: the saved pre-activation phase in revolutions (what the dX kernel takes the cos of, tests/dx_reference.py)."""
+        assert self.codec in ("ph8", "ph16")
+        return self.u.to(torch.float64) / (256.0 if self.codec == "ph8" else 65535.0)
+
 
 def decode_workspaces(dpre, acts, n_points, feat, tau, fmt):
     """-> (rows: {dpre fragment: Operand}, cols: {act fragment (aux offset included): Operand}, emax table uint8 [entries, 16] or None)
