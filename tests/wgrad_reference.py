@@ -151,6 +151,9 @@ def _round_with_ambiguity(v, dtype, tol):
 # The sin accuracies below are assumptions, not documented bounds: the CDNA ISA guides give no error bound for v_sin_f32 / v_sin_f16.  They
 # are what the kernels have met on MI355X so far (captured and synthetic workspaces, tests/test_hip_wgrad_reference.py): a hardware sin
 # further from the true value than assumed would show there as a gate failure, not pass unnoticed.
+EPS_SIN = 2.0 ** -19      # v_sin_f32: taken to be within this of the true sine (tests/fwd_reference.py makes the same assumption)
+
+
 def model_operand(op, kernel, g=None):
     """(value, ambiguity) of what ``kernel`` multiplies for this operand.  ``g`` (wgrad9 only): the exponent E_max the kernel fitted fp16's
     range to for this operand (a row pair's, or the feats columns'), per point [P, 1] -- it changes along the slices."""
@@ -161,7 +164,7 @@ def model_operand(op, kernel, g=None):
         if op.codec == "mx":   # mx8_value: fma(u, s, -128 s), s = 2^(E-133) built as bits (E - 6) << 23: E = 6 decodes as 0; exact in bf16
             return torch.where(op.e > 6, op.exact(), z), z
         # v_sin_f32 of the phase, packed to bf16 (RNE): v_sin_f32 taken to be within 2^-19 of sin (assumed, see above)
-        return _round_with_ambiguity(op.exact(), torch.bfloat16, 2.0 ** -19)
+        return _round_with_ambiguity(op.exact(), torch.bfloat16, EPS_SIN)
     assert kernel == "wgrad9"
     if op.codec == "mx":   # fp16 (u - 128) * 2^(E - er + 20 - 15), er = g - 20 ... a lane whose exponent field E - (g - 20) <= 0 flushes to 0
         keep = (op.e - (g - 20)) > 0
