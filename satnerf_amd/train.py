@@ -17,6 +17,9 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import ops, packing, step_plan
+from .rendering import _as_satnerf, _mode_of, render_rays, validate_ts
+
 
 _VOTES = 0  # capture votes taken by this process (Trainer._any_rank): the rendezvous store's keys are job-global
 
@@ -27,9 +30,6 @@ def _fmt_of(args):
     32 = parity-grade backward: fp32 saved activations and 3-pass (hi/lo split) bf16 GEMMs for dX and dW, i.e. the
     layer-by-layer path (satnerf_amd.generic) in ``bf16x3`` -- gradients within 2e-4 of the reference's (the fused backward's
     single-pass bf16 GEMMs: 7e-3), several times slower."""
-    from . import ops
-    from .rendering import _mode_of
-
     fmt = getattr(args, "bwd_fmt", None)
     fmt = ops.default_fmt(_mode_of(args)) if fmt is None else int(fmt)
     if fmt not in (8, 16, 32):
@@ -191,13 +191,11 @@ class Trainer:
                           "by 0.9 per epoch and trains sat-nerf with SNerfLoss for 2 epochs -- pass steps_per_epoch = len(dataset) // batch_size",
                           stacklevel=2)
         if self._snerf:  # s-nerf trains on the Sat-NeRF kernels: dead uncertainty head, 1-row zero embedding, SNerfLoss throughout
-            from .rendering import _as_satnerf
-
             models, args = _as_satnerf(models, args)
         self.models, self.args, self.world, self.lr = models, args, world_size, lr
         # the gradient all-reduce runs when there is more than one rank -- or, with SATNERF_FORCE_ALLREDUCE=1, also on a 1-rank
         # process group (how the single-GPU test box exercises the captured RCCL path)
-        self._collective = world_size > 1 or (os.environ.get("SATNERF_FORCE_ALLREDUCE", "0") == "1" and dist.is_available() and dist.is_initialized())
+        self._collective = step_plan.collective(world_size, dist.is_available() and dist.is_initialized())
         self.lr0, self.lr_gamma, self.steps_per_epoch, self.warmup_epochs = lr, lr_gamma, steps_per_epoch, warmup_epochs
         self.lr_steps_per_epoch = lr_steps_per_epoch if lr_steps_per_epoch else steps_per_epoch
         if args.model == "sat-nerf" and args.n_importance > 0 and loss_fn is None:
@@ -219,8 +217,6 @@ class Trainer:
         self._seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
         self._adam_in_graph = False
         self.loss_fn = loss_fn
-        from .rendering import _mode_of
-
         self.direct = (loss_fn is None and p.is_cuda and args.n_importance == 0 and args.model == "sat-nerf"
                        and hasattr(models["coarse"], "fused_training") and models["coarse"].fused_training(_mode_of(args), _fmt_of(args)))
         self.use_graph = use_graph and self.direct
@@ -230,14 +226,11 @@ class Trainer:
         if self.direct and mods[0] is models["coarse"] and len(mods) == 2 and mods[1] is models.get("t"):
             import numpy as np
 
-            from . import packing
-
             gidx = packing.backward_maps(models["coarse"].feat, models["coarse"].t_embedding_dims)["gidx"]
             late = np.concatenate([np.nonzero(gidx < 0)[0], np.arange(gidx.size, p.numel())])
             self._late_idx = torch.from_numpy(late.astype(np.int32)).to(p.device)
         self._graph, self._static, self._graph_banks = None, None, None
-        self._pre_setup, self._pre_bufs = None, None
-        self._pack_in_tail, self._gather_in_fwd, self._packed_version = False, None, None
+        self._pre_bufs, self._pack_in_tail, self._packed_version = None, False, None
         self.max_inflight = int(os.environ.get("SATNERF_MAX_INFLIGHT", "0"))
         self.pace_every = max(1, int(os.environ.get("SATNERF_PACE_EVERY", "1")))
         self.last_rgb = None
@@ -246,66 +239,66 @@ class Trainer:
         # reference run's draws so that two trainings differ by their arithmetic only
         self.jitter = lambda n, s, device: torch.rand(n, s, device=device)
 
-    # ---- forward + loss + backward on the current stream, gradients accumulate into the flat buffer -------------------
-    def _forward_backward(self, rays, ts, rgbs, depth=None):
-        """Colour pass [+ depth-supervision pass] [+ in-graph Adam]; returns the per-block loss partial sums."""
-        from . import ops
-        from .rendering import _mode_of
+    def _pass(self, n, s, device):
+        """What the step's passes start from: (model, embedding, mode, width, embedding dims, saved-state format, workspace, sky head's weights)."""
+        model, fmt, sk = self.models["coarse"], _fmt_of(self.args), self.models["coarse"].sky_color
+        return (model, self.models["t"], _mode_of(self.args), model.feat, model.t_embedding_dims, fmt,
+                ops.acts_workspace(n * s, model.feat, device, fmt), (sk[0].weight.data, sk[0].bias.data, sk[2].weight.data, sk[2].bias.data))
 
+    def _plan(self, bank=None, captured=True):
+        """The launch plan of a step [on ``bank``] (step_plan.launches) under the environment's switches, read now, and the flags of the
+        trainer's capture -- ``captured=False``: none of them, for questions a capture does not enter (and that a replay may ask)."""
+        flags = dict(kernel_rng=self._kernel_rng, adam_in_graph=self._adam_in_graph, pack_in_tail=self._pack_in_tail) if captured else {}
+        return step_plan.launches(collective=self._collective, fmt=_fmt_of(self.args), n_samples=self.args.n_samples, snerf=self._snerf,
+                                  render_fused_ok=ops.render_fused_ok(self.models["coarse"].feat, _mode_of(self.args), self.args.n_samples),
+                                  bank=bank is not None, ray_bank=type(bank).__name__ == "RayBank", late_idx=self._late_idx is not None, **flags)
+
+    def _fused_forward(self):
+        """True when the colour pass's forward is ONE launch (sr_satnerf_render_train), step_plan.fused_forward."""
+        return self._plan(captured=False).fused_forward
+
+    # ---- forward + loss + backward on the current stream, gradients accumulate into the flat buffer -------------------
+    def _forward_backward(self, rays, ts, rgbs, depth=None, source=None):
+        """Colour pass [+ depth-supervision pass] [+ in-graph Adam]; returns the per-block loss partial sums.  ``source`` = what
+        ``_gather_from_banks`` returned for a captured step's colour batch; None = rays / ts / rgbs as given."""
         if self._snerf:  # (also inside a captured step, whose static ts may hold a bank's image ids)
             ts = self._zero_ts(ts)
             if depth is not None:
                 depth = (depth[0], self._zero_ts(depth[1]), depth[2])
-        model, emb = self.models["coarse"], self.models["t"]
-        args = self.args
-        n, s = rays.shape[0], args.n_samples
-        mode = _mode_of(args)
-        feat, tau = model.feat, model.t_embedding_dims
-        ticking = self._kernel_rng or self._adam_in_graph
-        # r05, single-GPU captured step: no sr_pack_all launch -- the launch that updates the parameters (sr_grad_tail_adam) also writes
-        # them into the weight streams, and the forward, now the step's first launch, ticks the step counter itself ("tick first")
-        pit = self._pack_in_tail and ticking
-        if pit:
-            hi, lo, l0, bstream, maps = model.packed_static(mode)
-        else:
-            model.repack(mode, backward=True, tick=self.adam_state if ticking else None)
+        n, s = rays.shape[0], self.args.n_samples
+        model, emb, mode, feat, tau, fmt, acts, sw = self._pass(n, s, rays.device)
+        plan = self._plan()
+        if plan.pack_first:
+            model.repack(mode, backward=True, tick=self.adam_state if plan.pack_first == "ticks" else None)
             hi, lo, l0 = model.packed(mode)
             bstream, maps = model.packed_backward()
+        else:  # (step_plan.launches: the update launch keeps the static streams current, the forward opens the step)
+            hi, lo, l0, bstream, maps = model.packed_static(mode)
         sk = model.sky_color
         # stratified jitter (rendering.py:77): torch's generator when run eagerly; inside a captured step the kernel draws it
         # itself (Philox keyed by the seed, stepping with the device counter) -- one launch and the graph's RNG bookkeeping less
         u = None if self._kernel_rng else self.jitter(n, s, rays.device)
-        noise_std = float(args.noise_std)
+        noise_std = float(self.args.noise_std)
         # models/satnerf.py:58 draws randn even when noise_std == 0; the draw is skipped then (results are identical)
         nz = torch.randn(n, s, device=rays.device) if noise_std != 0 else None
-        fmt = _fmt_of(args)
-        acts = ops.acts_workspace(n * s, feat, rays.device, fmt)
-        sc_on = float(getattr(args, "sc_lambda", 0.0)) > 0
+        sc_on = float(getattr(self.args, "sc_lambda", 0.0)) > 0
         # ONE launch for the forward (sr_satnerf_render_train): stratified depths + sky head in the prologue, MLP saving the 8-bit
         # state, compositing + colour loss + compositing backward in the epilogue -- r04 ran sr_ray_setup, the MLP and sr_render_loss
         # as three launches; the per-ray functions are the same, the results bit-identical.  SATNERF_TRAIN_FUSED=0: the three launches (A/B)
-        fused = self._pre_setup is None and self._fused_forward()
-        gather, self._gather_in_fwd = self._gather_in_fwd, None
-        if pit and not fused:
-            raise RuntimeError("pack-in-tail steps need the one-launch training forward (it ticks the step counter)")
-        if fused:
-            # gather: the captured step samples its batch INSIDE this launch (the bank's cursor over the epoch's shuffled rows): rays / ts /
+        if plan.fused_forward:
+            # source: the captured step samples its batch INSIDE this launch (the bank's cursor over the epoch's shuffled rows): rays / ts /
             # rgbs -- the graph's static batch tensors -- are then OUTPUTS of the launch, read by the step's later launches
-            src = (gather["bank"].rays, gather["bank"].ts, gather["bank"].rgbs) if gather is not None else (rays, ts, rgbs)
-            r = ops.render_train(src[0], src[1], emb.weight.data, s, feat, tau, mode, hi, lo, l0, sk[0].weight.data, sk[0].bias.data, sk[2].weight.data,
-                                 sk[2].bias.data, src[2], acts, u=u, noise=nz, noise_std=noise_std, seed=self._seed, step_counter=self.adam_state,
-                                 sched=self.sched, want_z=sc_on, tick=2 if pit else 0,
-                                 gather=None if gather is None else dict(idx=gather["idx"], cursor=gather["cursor"], batches=gather["batches"],
+            src = (source["bank"].rays, source["bank"].ts, source["bank"].rgbs) if source is not None else (rays, ts, rgbs)
+            r = ops.render_train(src[0], src[1], emb.weight.data, s, feat, tau, mode, hi, lo, l0, *sw, src[2], acts, u=u, noise=nz, noise_std=noise_std,
+                                 seed=self._seed, step_counter=self.adam_state, sched=self.sched, want_z=sc_on, tick=plan.tick,
+                                 gather=None if source is None else dict(idx=source["idx"], cursor=source["cursor"], batches=source["batches"],
                                                                          out=(rays, rgbs, ts)))
             z, sky, loss, self.last_rgb = r["z"], r["sky"], r["loss"], r["rgb"]
             albedo, sigma, sun_v, beta = r["albedo"].view(-1, 3), r["sigma"].view(-1), r["sun_v"].view(-1), r["beta"].view(-1)
             d_sigma, d_albedo, d_sun, g_beta, d_sky = r["d_sigma"], r["d_albedo"], r["d_sun"], r["g_beta"], r["d_sky"]
         else:
-            if self._pre_setup is not None:  # a captured step whose gather launch already produced them (_gather_from_banks)
-                (z, sky), self._pre_setup = self._pre_setup, None
-            else:
-                z, sky = ops.ray_setup(rays, u, s, sk[0].weight.data, sk[0].bias.data, sk[2].weight.data, sk[2].bias.data, seed=self._seed,
-                                       step_counter=self.adam_state)
+            # source: a captured step whose gather launch already produced them (_gather_from_banks)
+            z, sky = source if source is not None else ops.ray_setup(rays, u, s, *sw, seed=self._seed, step_counter=self.adam_state)
             albedo, sigma, sun_v, beta = ops.satnerf_mlp(rays[:, 0:3], rays[:, 3:6], rays[:, 8:11], z, emb.weight.data, ts, n * s, s, feat, tau, mode,
                                                          hi, lo, l0, acts=acts, fmt=fmt)
             if s <= 64:  # one launch: compositing forward -> loss -> compositing backward
@@ -319,7 +312,7 @@ class Trainer:
                                                                    weights, transp, g_rgb, None, g_w, None)
                 self.last_rgb = rgb
         dpre, d_t = ops.satnerf_mlp_bwd(feat, tau, n * s, bstream, acts, albedo, sigma, sun_v, beta, d_albedo, d_sigma, d_sun, g_beta.view(-1), fmt=fmt)
-        partial, plan = ops.wgrad_partials(feat, tau, n * s, dpre, acts, maps["blocks"], fmt, maps["loads8"])
+        partial, wplan = ops.wgrad_partials(feat, tau, n * s, dpre, acts, maps["blocks"], fmt, maps["loads8"])
         # the colour pass's gradient tail comes LAST: the solar-correction and depth-supervision passes accumulate their weight gradients
         # into the (zeroed) flat buffer first, the tail adds the colour pass's on top -- and, on a single GPU under graph capture, applies
         # Adam in the same launch (sr_grad_tail_adam: the thread that reduces a parameter's split-K slices updates it and zeroes its
@@ -328,100 +321,70 @@ class Trainer:
             loss = torch.cat([loss.view(-1), self._sc_pass(rays, ts, z, noise_std).view(-1)])
         if depth is not None:
             loss = torch.cat([loss.view(-1), self._depth_pass(*depth, noise_std * 0.9).view(-1)])  # main.py:132 decays the noise first
-        tail = (partial, plan, maps["gidx"], maps["gscale"], model.flat_grads(), rays[:, 8:11], sk[0].weight.data, sk[0].bias.data,
-                sk[2].weight.data, sky, d_sky, sk[0].weight.grad, sk[0].bias.grad, sk[2].weight.grad, sk[2].bias.grad, d_t, ts, n, s, tau,
-                emb.weight.grad)
-        if self._adam_in_graph and not self._collective and self._late_idx is not None and os.environ.get("SATNERF_TAIL_ADAM", "1") != "0":
+        tail = (partial, wplan, maps["gidx"], maps["gscale"], model.flat_grads(), rays[:, 8:11], *sw[:3], sky, d_sky, sk[0].weight.grad,
+                sk[0].bias.grad, sk[2].weight.grad, sk[2].bias.grad, d_t, ts, n, s, tau, emb.weight.grad)
+        if plan.tail == "tail_adam":
             # lr < 0: the kernel reads the current rate from sched[1], so a scheduler can change it under graph replay
             ops.grad_tail_adam(*tail, self.state.params, self.exp_avg, self.exp_avg_sq, self._late_idx, self.adam_state, lr=-1.0,
-                               grad_scale=1.0 / self.world, pack=model.pack_scatter(mode) if pit else None)
+                               grad_scale=1.0 / self.world, pack=None if plan.pack_first else model.pack_scatter(mode))
             return loss
-        if pit and not self._collective:
-            raise RuntimeError("single-GPU pack-in-tail steps end in sr_grad_tail_adam")
         # data parallel (r06): the N > 1 step is the N = 1 step split at the collective -- sr_grad_tail (the reduction) | all-reduce of the flat
-        # gradient | sr_adam_step_pack (Adam + the re-pack of the weight streams, `_update_and_pack`): no sr_pack_all, no separate Adam launch
+        # gradient | sr_adam_step_pack (Adam + the re-pack of the weight streams, `_update`): no sr_pack_all, no separate Adam launch
         ops.grad_tail(*tail)
-        if self._adam_in_graph:  # the update rides in the same graph (the RCCL all-reduce captured with it, or the A/B switch above)
-            if self._collective:
-                dist.all_reduce(self.state.grads, op=dist.ReduceOp.SUM)
-            if pit:
-                self._update_and_pack()
-            else:
-                ops.adam_step_graph(self.state.params, self.state.grads, self.exp_avg, self.exp_avg_sq, self.adam_state, lr=-1.0,
-                                    grad_scale=1.0 / self.world, zero_grad=True)
+        if not plan.update_after_replay:  # the update rides in the same graph (the RCCL all-reduce captured with it, or SATNERF_TAIL_ADAM=0)
+            self._update(plan.update)
         return loss
 
-    def _update_and_pack(self):
-        """(data-parallel pack-in-tail steps, after the all-reduce) Adam over the flat buffers with the device-side step count / rate, each
-        coarse-model parameter written into the weight streams by the same launch."""
-        from . import ops
-        from .rendering import _mode_of
-
-        ops.adam_step_pack(self.state.params, self.state.grads, self.exp_avg, self.exp_avg_sq, self.adam_state,
-                           pack=self.models["coarse"].pack_scatter(_mode_of(self.args)), lr=-1.0, grad_scale=1.0 / self.world, zero_grad=True)
-
-    def _fused_forward(self):
-        """True when the colour pass's forward is ONE launch (sr_satnerf_render_train): 8-bit saved state, <= 64 samples dividing a
-        workgroup's points, a generated-core build for (width, mode)."""
-        from . import ops
-        from .rendering import _mode_of
-
-        s, mode = self.args.n_samples, _mode_of(self.args)
-        return (_fmt_of(self.args) == 8 and s <= 64 and ops.render_fused_ok(self.models["coarse"].feat, mode, s)
-                and os.environ.get("SATNERF_TRAIN_FUSED", "1") != "0" and os.environ.get("SATNERF_FWD_V1", "0") != "1")
+    def _update(self, update):
+        """[The all-reduce of the flat gradient and] the update launch ``update`` (step_plan.launches) names; lr < 0: the device-side rate."""
+        if self._collective:
+            dist.all_reduce(self.state.grads, op=dist.ReduceOp.SUM)
+        bufs, kw = (self.state.params, self.state.grads, self.exp_avg, self.exp_avg_sq), dict(grad_scale=1.0 / self.world, zero_grad=True)
+        if update == "adam_pack":
+            ops.adam_step_pack(*bufs, self.adam_state, pack=self.models["coarse"].pack_scatter(_mode_of(self.args)), lr=-1.0, **kw)
+        elif update == "adam_graph":
+            ops.adam_step_graph(*bufs, self.adam_state, lr=-1.0, **kw)
+        else:
+            ops.adam_step(*bufs, self.n_steps, lr=self.lr, **kw)
 
     def _sc_pass(self, rays, ts, z, noise_std):
         """Solar correction (rendering.py:102-108, metrics.py:27-34): the SAME depths along the sun direction; transparency and
         weights of that pass are detached, so only sun visibility receives a gradient."""
-        from . import ops
-        from .rendering import _mode_of
-
-        model, emb, args = self.models["coarse"], self.models["t"], self.args
         n, s = z.shape
-        mode = _mode_of(args)
-        feat, tau = model.feat, model.t_embedding_dims
+        model, emb, mode, feat, tau, fmt, acts, _ = self._pass(n, s, rays.device)
         hi, lo, l0 = model.packed(mode)
         bstream, maps = model.packed_backward()
         nz = torch.randn(n, s, device=rays.device) if noise_std != 0 else None
-        fmt = _fmt_of(args)
-        acts = ops.acts_workspace(n * s, feat, rays.device, fmt)
-        albedo, sigma, sun_v, beta = ops.satnerf_mlp(rays[:, 0:3], rays[:, 8:11], rays[:, 8:11], z, emb.weight.data, ts, n * s, s, feat, tau, mode,
-                                                     hi, lo, l0, acts=acts, fmt=fmt)
-        loss, d_sun = ops.sc_loss(z, sigma.view(n, s), nz, noise_std, sun_v.view(n, s), float(args.sc_lambda))
-        dpre, _ = ops.satnerf_mlp_bwd(feat, tau, n * s, bstream, acts, albedo, sigma, sun_v, beta, None, None, d_sun, None, want_dt=False, fmt=fmt)
-        ops.satnerf_wgrad(feat, tau, n * s, dpre, acts, maps["blocks"], maps["gidx"], maps["gscale"], model.flat_grads(), accumulate=True, fmt=fmt,
-                          loads=maps["loads8"])
+        heads = ops.satnerf_mlp(rays[:, 0:3], rays[:, 8:11], rays[:, 8:11], z, emb.weight.data, ts, n * s, s, feat, tau, mode, hi, lo, l0, acts=acts,
+                                fmt=fmt)
+        loss, d_sun = ops.sc_loss(z, heads[1].view(n, s), nz, noise_std, heads[2].view(n, s), float(self.args.sc_lambda))
+        self._accumulate_wgrads(model, n * s, bstream, maps, acts, fmt, heads, None, d_sun)
         return loss
 
     def _depth_pass(self, rays, ts, depths, noise_std):
         """Depth supervision (main.py:134-141): render the depth batch, loss = ds_lambda/3 * mean(w * (depth - target)^2)
         (metrics.py:75-92); only sigma receives a gradient, so the MLP backward runs with the other head gradients absent."""
-        from . import ops
-        from .rendering import _mode_of
-
-        model, emb, args = self.models["coarse"], self.models["t"], self.args
-        n, s = rays.shape[0], args.n_samples
-        mode = _mode_of(args)
-        feat, tau = model.feat, model.t_embedding_dims
+        n, s = rays.shape[0], self.args.n_samples
+        model, emb, mode, feat, tau, fmt, acts, sw = self._pass(n, s, rays.device)
         hi, lo, l0 = model.packed(mode)
         bstream, maps = model.packed_backward()
-        sk = model.sky_color
         u = None if self._kernel_rng else self.jitter(n, s, rays.device)
         nz = torch.randn(n, s, device=rays.device) if noise_std != 0 else None
-        z, sky = ops.ray_setup(rays, u, s, sk[0].weight.data, sk[0].bias.data, sk[2].weight.data, sk[2].bias.data, seed=self._seed + 1,
-                               step_counter=self.adam_state)
-        fmt = _fmt_of(args)
-        acts = ops.acts_workspace(n * s, feat, rays.device, fmt)
-        albedo, sigma, sun_v, beta = ops.satnerf_mlp(rays[:, 0:3], rays[:, 3:6], rays[:, 8:11], z, emb.weight.data, ts, n * s, s, feat, tau, mode,
-                                                     hi, lo, l0, acts=acts, fmt=fmt)
-        weights, transp, depth, _ = ops.composite(z, sigma.view(n, s), nz, noise_std, albedo.view(n, s, 3), sun_v.view(n, s), sky)
-        loss, g_depth = ops.depth_loss(depth, depths, float(args.ds_lambda), use_weights=not getattr(args, "ds_noweights", False))
-        d_sigma, _, _, _ = ops.composite_bwd(z, sigma.view(n, s), nz, noise_std, albedo.view(n, s, 3), sun_v.view(n, s), sky, weights, transp,
-                                             None, g_depth, None, None)
-        dpre, _ = ops.satnerf_mlp_bwd(feat, tau, n * s, bstream, acts, albedo, sigma, sun_v, beta, None, d_sigma, None, None, want_dt=False, fmt=fmt)
-        ops.satnerf_wgrad(feat, tau, n * s, dpre, acts, maps["blocks"], maps["gidx"], maps["gscale"], model.flat_grads(), accumulate=True, fmt=fmt,
-                          loads=maps["loads8"])
+        z, sky = ops.ray_setup(rays, u, s, *sw, seed=self._seed + 1, step_counter=self.adam_state)
+        heads = ops.satnerf_mlp(rays[:, 0:3], rays[:, 3:6], rays[:, 8:11], z, emb.weight.data, ts, n * s, s, feat, tau, mode, hi, lo, l0, acts=acts,
+                                fmt=fmt)
+        albedo, sigma, sun_v = heads[0].view(n, s, 3), heads[1].view(n, s), heads[2].view(n, s)
+        weights, transp, depth, _ = ops.composite(z, sigma, nz, noise_std, albedo, sun_v, sky)
+        loss, g_depth = ops.depth_loss(depth, depths, float(self.args.ds_lambda), use_weights=not getattr(self.args, "ds_noweights", False))
+        d_sigma, _, _, _ = ops.composite_bwd(z, sigma, nz, noise_std, albedo, sun_v, sky, weights, transp, None, g_depth, None, None)
+        self._accumulate_wgrads(model, n * s, bstream, maps, acts, fmt, heads, d_sigma, None)
         return loss
+
+    def _accumulate_wgrads(self, model, n, bstream, maps, acts, fmt, heads, d_sigma, d_sun):
+        """How the solar-correction and depth passes end: dX from the one head gradient the pass has, weight gradients ADDED to the flat buffer."""
+        dpre, _ = ops.satnerf_mlp_bwd(model.feat, model.t_embedding_dims, n, bstream, acts, *heads, None, d_sigma, d_sun, None, want_dt=False, fmt=fmt)
+        ops.satnerf_wgrad(model.feat, model.t_embedding_dims, n, dpre, acts, maps["blocks"], maps["gidx"], maps["gscale"], model.flat_grads(),
+                          accumulate=True, fmt=fmt, loads=maps["loads8"])
 
     # ---- schedule (main.py:86-94,128-131) ------------------------------------------------------------------------------------
     def current_epoch(self):
@@ -531,57 +494,44 @@ class Trainer:
                 m.mark_weights_changed()
 
     def _gather_from_banks(self):
-        """(inside the captured step) every bank gathers its next batch into the static inputs and moves its device cursor on"""
-        from . import ops
-
+        """(inside the captured step) every bank gathers its next batch into the static inputs and moves its device cursor on; returns the colour
+        batch's source: None (gathered here), the description of the gather the forward launch does itself, or sr_gather_setup's (z, sky)."""
+        sampler, source = self._plan(self._graph_banks[0]).sampler, None
         for k, b in enumerate(self._graph_banks):
             idx, cursor, batches = b.graph_source()
             out = self._static[3 * k:3 * k + 3]
-            if (k == 0 and self._kernel_rng and self._fused_forward() and not self._snerf and type(b).__name__ == "RayBank"
-                    and os.environ.get("SATNERF_GATHER_IN_FWD", "1") != "0"):
+            if k == 0 and sampler == "forward":
                 # the colour batch is sampled by the forward launch itself (sr_satnerf_render_train's gather): no launch here
-                self._gather_in_fwd = dict(bank=b, idx=idx, cursor=cursor, batches=batches)
-            elif k == 0 and self._kernel_rng and not self._fused_forward():
+                source = dict(bank=b, idx=idx, cursor=cursor, batches=batches)
+            elif k == 0 and sampler == "setup":
                 # the colour batch: gather + stratified depths + sky colour in ONE launch (sr_gather_setup); _forward_backward then
                 # skips its ray set-up launch (when the forward is not the one-launch training render, which sets the rays up itself).
                 # step_offset 1: this runs before sr_pack_all ticks the step counter
-                model, n, s = self.models["coarse"], out[0].shape[0], self.args.n_samples
+                sk, n, s = self.models["coarse"].sky_color, out[0].shape[0], self.args.n_samples
                 if self._pre_bufs is None or self._pre_bufs[0].shape != (n, s):
                     dev = out[0].device
                     self._pre_bufs = (torch.empty(n, s, device=dev), torch.empty(n, 3, device=dev))
-                sk = model.sky_color
                 ops.gather_setup(b.rays, b.rgbs, b.ts, idx, out, s, sk[0].weight.data, sk[0].bias.data, sk[2].weight.data, sk[2].bias.data,
                                  self._pre_bufs[0], self._pre_bufs[1], self._seed, self.adam_state, step_offset=1, cursor=cursor, batches=batches)
-                self._pre_setup = self._pre_bufs
+                source = self._pre_bufs
             else:
                 ops.gather_batch(b.rays, b.rgbs, b.ts, idx, out=out, cursor=cursor, batches=batches)
+        return source
 
     def _capture(self, inputs, banks=None):
         self._static = tuple(t.clone() for t in inputs)
         self._graph_banks = tuple(banks) if banks else None
-        # data parallel: with the RCCL backend ("nccl") the gradient all-reduce and the Adam update CAN be captured into the step's graph
-        # (NCCL / RCCL collectives are capturable): a step is then one replay, no eager launches between steps.  It is OPT-IN
-        # (SATNERF_GRAPH_ALLREDUCE=1) until a job with two or more GPUs has run it: so far it has only executed on a 1-rank group
-        # (tests/test_hip_training.py), and a collective that misbehaves inside a replayed graph hangs the job instead of raising
-        # (ADVICE r03).  Default, other backends (gloo cannot be captured), or a capture that fails on any rank: the eager all-reduce +
-        # Adam issued after the replay.
-        capture_collective = (self._collective and os.environ.get("SATNERF_GRAPH_ALLREDUCE", "0") == "1" and dist.is_initialized()
-                              and dist.get_backend() == "nccl" and not getattr(self, "_collective_capture_failed", False))
-        self._adam_in_graph = (not self._collective) or capture_collective
-        self._kernel_rng = float(self.args.noise_std) == 0.0  # (a noisy step still draws randn from torch's generator)
-        # the launch that updates the parameters re-packs the weight streams and the forward opens the step (no sr_pack_all launch): on a
-        # single GPU that launch is the gradient tail (sr_grad_tail_adam), with a collective it is sr_adam_step_pack behind the all-reduce
-        # (in the graph when the collective is captured, eagerly after the replay otherwise).  SATNERF_DP_PACK=0: the r05 N > 1 step (A/B)
-        self._pack_in_tail = (self._late_idx is not None and self._kernel_rng and self._fused_forward()
-                              and os.environ.get("SATNERF_TAIL_ADAM", "1") != "0" and os.environ.get("SATNERF_TAIL_PACK", "1") != "0"
-                              and (not self._collective or os.environ.get("SATNERF_DP_PACK", "1") != "0"))
+        # what this capture holds (step_plan.capture_state; the flags persist into later eager steps)
+        pg = dist.is_available() and dist.is_initialized()
+        self._kernel_rng, capture_collective, self._adam_in_graph, self._pack_in_tail = step_plan.capture_state(
+            noise_zero=float(self.args.noise_std) == 0.0, collective=self._collective, pg_initialised=pg, backend=dist.get_backend() if pg else None,
+            capture_failed=getattr(self, "_collective_capture_failed", False), late_idx=self._late_idx is not None, fused_forward=self._fused_forward())
         if self._pack_in_tail:
             self._repack_static()
         snapshot = (self.state.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.adam_state.clone())
         def run():
-            if self._graph_banks:
-                self._gather_from_banks()
-            return self._forward_backward(*self._static[:3], depth=self._static[3:] or None)
+            source = self._gather_from_banks() if self._graph_banks else None
+            return self._forward_backward(*self._static[:3], depth=self._static[3:] or None, source=source)
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -598,8 +548,6 @@ class Trainer:
             b.graph_reset()
         if self._pack_in_tail:               # ... and left the warm-up's weights in the streams
             self._repack_static()
-        from . import ops
-
         self._graph = torch.cuda.CUDAGraph()
         failed = False
         try:
@@ -624,8 +572,6 @@ class Trainer:
     def _repack_static(self):
         """(pack-in-tail steps) one eager sr_pack_all into the static stream buffers: at capture time, and whenever somebody other than the
         step's own optimizer launch changed the weights (load_state_dict, a manual edit) -- the step itself keeps them current."""
-        from .rendering import _mode_of
-
         model = self.models["coarse"]
         model.repack(_mode_of(self.args), backward=True, tick=None)
         self._packed_version = model.weights_version()
@@ -663,27 +609,19 @@ class Trainer:
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self._vote_group)
             return bool(t.item())
 
-    def _sampler_in_forward(self, banks):
-        """True when a captured step can sample its colour batch inside the forward launch (sr_satnerf_render_train's gather)."""
-        return (self._fused_forward() and not self._snerf and type(banks[0]).__name__ == "RayBank"
-                and os.environ.get("SATNERF_GATHER_IN_FWD", "1") != "0")
-
     def step_from_bank(self, bank, depth_bank=None):
         """One step on the banks' next batches; with a captured graph the batches are gathered straight into its static inputs."""
         shapes = (bank.batch_size,) + ((depth_bank.batch_size,) if depth_bank is not None else ())
-        from .rendering import validate_ts
-
         for b in (bank, depth_bank):  # image indices are checked once per bank (nn.Embedding would raise on a bad one)
             if b is not None and not self._snerf and not getattr(b, "_ts_validated", False):
                 validate_ts(b.ts, self.models)
                 b._ts_validated = True
         banks = (bank,) + ((depth_bank,) if depth_bank is not None else ())
         if (self.direct and self.use_graph and float(self.args.noise_std) == 0.0 and all(b.drop_last for b in banks)
-                and os.environ.get("SATNERF_GRAPH_SAMPLER", "1" if self._sampler_in_forward(banks) else "0") == "1"):
+                and self._plan(bank, captured=False).graph_sampler):
             # the captured step samples for itself (device cursors over the epoch's shuffled indices): a step is ONE graph replay with no
-            # eager launch and no host-side index arithmetic.  ON by default when the forward launch can do the sampling itself
-            # (_sampler_in_forward: r05, sr_satnerf_render_train's gather); otherwise opt-in (SATNERF_GRAPH_SAMPLER=1) -- as separate
-            # gather launches in the graph it is exactly as fast as the eager gather in front of the replay (r02: 0.420-0.425 ms either way)
+            # eager launch and no host-side index arithmetic.  ON by default when the forward launch can do the sampling itself (r05,
+            # sr_satnerf_render_train's gather); otherwise opt-in (step_plan.launches: graph_sampler)
             if self._graph is None or getattr(self, "_graph_banks", None) is None or tuple(map(id, self._graph_banks)) != tuple(map(id, banks)):
                 first = [b.gather(b.graph_source()[0][:b.batch_size]) for b in banks]
                 self._apply_schedule()
@@ -709,8 +647,6 @@ class Trainer:
         (pass None once past ``ds_drop``: main.py:138 stops adding the term).  ``validate=False`` skips the range check of the image
         indices (one device reduction + a host sync per step, rendering.validate_ts) for callers that have checked their ``ts`` once:
         the host then runs ahead of the replayed step again."""
-        from . import ops
-
         if depth is not None and not float(getattr(self.args, "ds_lambda", 0.0)) > 0:
             raise ValueError("a depth batch was passed but args.ds_lambda is not > 0 (main.py:51)")
         if self._snerf:  # image indices are not an input of s-nerf: every ray reads row 0 of the zero embedding
@@ -718,8 +654,6 @@ class Trainer:
             if depth is not None:
                 depth = (depth[0], self._zero_ts(depth[1]), depth[2])
         if not _inputs_in_place and validate:
-            from .rendering import validate_ts
-
             validate_ts(ts, self.models)
             if depth is not None:
                 validate_ts(depth[1], self.models)
@@ -743,20 +677,11 @@ class Trainer:
                 if self._pack_in_tail and self.models["coarse"].weights_version() != self._packed_version:
                     self._repack_static()
                 loss = self._forward_backward(*inputs[:3], depth=inputs[3:] or None)
-            in_graph = self._adam_in_graph and self._graph is not None and self.use_graph and float(self.args.noise_std) == 0.0
-            if self._collective and not self._adam_in_graph:
-                dist.all_reduce(self.state.grads, op=dist.ReduceOp.SUM)
             self.n_steps += 1
-            if not in_graph and not self._adam_in_graph:  # (an eager direct step after a capture already stepped Adam)
-                if self._pack_in_tail:  # the forward ticked the device-side step count; the update launch also re-packs the streams
-                    self._update_and_pack()
-                else:
-                    ops.adam_step(self.state.params, self.state.grads, self.exp_avg, self.exp_avg_sq, self.n_steps, lr=self.lr,
-                                  grad_scale=1.0 / self.world, zero_grad=True)
+            if not self._adam_in_graph:  # (otherwise the pass -- captured, or an eager direct step after a capture -- stepped Adam)
+                self._update("adam_pack" if self._pack_in_tail else "adam_eager")  # (step_plan.launches: update behind the replay)
             loss = _LazyLoss(loss)
         else:
-            from .rendering import render_rays
-
             res = render_rays(self.models, self.args, rays, ts)
             if self.loss_fn is not None:
                 loss_fn = self.loss_fn
@@ -790,8 +715,6 @@ class Trainer:
             if hasattr(m, "mark_weights_changed"):
                 m.mark_weights_changed()
         if self.direct and self._pack_in_tail:  # ... and the step's update launch re-packed the streams
-            from .rendering import _mode_of
-
             self.models["coarse"].note_packed(_mode_of(self.args))
             self._packed_version = self.models["coarse"].weights_version()
         self.args.noise_std *= 0.9  # main.py:132

@@ -292,3 +292,71 @@ def test_late_parameters_of_the_fused_tail_under_stress():
     print(f"late parameters over 400 launches: worst |difference| {worst:.2e} of an update of {moved:.2e}")
     assert worst <= 1e-3 * moved + 1e-9
     restore()
+
+
+# switches of the step (satnerf_amd/step_plan.py): every case starts from none of them set
+STEP_SWITCHES = ("SATNERF_TAIL_ADAM", "SATNERF_TAIL_PACK", "SATNERF_DP_PACK", "SATNERF_GATHER_IN_FWD", "SATNERF_TRAIN_FUSED", "SATNERF_FWD_V1",
+                 "SATNERF_GRAPH_SAMPLER", "SATNERF_GRAPH_ALLREDUCE", "SATNERF_FORCE_ALLREDUCE")
+HOST_ONLY = ("sr_wgrad_plan",)  # entry points that launch nothing: the split-K plan is made on the host
+# the rows of tests/test_step_plan_host.py's ADVERTISED that a single GPU runs: their switches, bwd_fmt, bank and hand-written launch names
+PLAN_CASES = ("single GPU", "r04 six launches", "tail then Adam", "three-launch forward, bank", "three-launch forward, bank, graph sampler", "bwd_fmt=16")
+
+
+@pytest.mark.parametrize("case", PLAN_CASES)
+def test_captured_step_launches_what_the_plan_names(monkeypatch, case):
+    """The launches a capture records are the ones the row names by hand -- and the ones ``Trainer._plan`` names (step_plan.launches) --
+    in order: every call through the C ABI (satnerf_amd._lib.call) made while ops.graph_capture is open, host-only entry points aside,
+    for one step_from_bank (one step without a bank) = one capture and one replay.  A single GPU has no collective: the whole of ``names``
+    is in the graph."""
+    import contextlib
+
+    from satnerf_amd import _lib, ops
+    from satnerf_amd.data import RayBank
+    from satnerf_amd.models import load_model
+    from satnerf_amd.train import Trainer
+
+    from .test_step_plan_host import ADVERTISED
+
+    row, want = ADVERTISED[case]
+    switches, bwd_fmt, with_bank = row.get("env", {}), row.get("fmt"), row.get("bank", "RayBank") is not None
+    for name in STEP_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    recorded, recording = [], [False]
+    real_call, real_capture = _lib.call, ops.graph_capture
+
+    def call(name, *args):
+        if recording[0]:
+            recorded.append(name)
+        return real_call(name, *args)
+
+    @contextlib.contextmanager
+    def capture(graph):
+        with real_capture(graph):
+            recording[0] = True
+            try:
+                yield
+            finally:
+                recording[0] = False
+
+    monkeypatch.setattr(_lib, "call", call)
+    monkeypatch.setattr(ops, "graph_capture", capture)
+    n_bank, bs = 4 * 128 + 9, 128
+    rays, ts = O.synthetic_rays(n_bank, seed=34)
+    rgbs = torch.rand(n_bank, 3, generator=torch.Generator().manual_seed(35))
+    torch.manual_seed(0)
+    args = O.default_args(mlp_mode="bf16") if bwd_fmt is None else O.default_args(mlp_mode="bf16", bwd_fmt=bwd_fmt)
+    tr = Trainer({"coarse": load_model(args).to(DEV), "t": torch.nn.Embedding(30, 4).to(DEV)}, args, steps_per_epoch=1000)
+    bank = RayBank(rays.to(DEV), rgbs.to(DEV), ts.to(DEV), bs, seed=9) if with_bank else None
+    if with_bank:
+        loss = tr.step_from_bank(bank).item()
+    else:
+        loss = tr.step(rays[:bs].to(DEV), ts[:bs].to(DEV), rgbs[:bs].to(DEV)).item()
+    torch.cuda.synchronize()
+    plan = tr._plan(bank)
+    print(case, [n for n in recorded if n not in HOST_ONLY], plan.names)
+    assert tr._graph is not None and loss == loss and int(tr.adam_state[0].item()) == 1
+    assert "all_reduce" not in plan.names and not plan.update_after_replay
+    assert tuple(n for n in recorded if n not in HOST_ONLY) == want == plan.names
+    assert (tr._graph_banks is not None) == (with_bank and plan.graph_sampler)

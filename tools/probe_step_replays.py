@@ -36,8 +36,7 @@ for K in (2, 4, 8):
     gk = torch.cuda.CUDAGraph()
     with ops.graph_capture(gk):
         for _ in range(K):
-            tr._gather_from_banks()
-            tr._forward_backward(*tr._static[:3])
+            tr._forward_backward(*tr._static[:3], source=tr._gather_from_banks())
     graphs[K] = gk
 def multi(K):
     def fn():
