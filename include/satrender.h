@@ -385,6 +385,16 @@ int sr_latlonalt_from_depth(const float* rays, int ray_stride, const float* dept
 int sr_rpc_rays(const double* rpc, int width, int height, double min_alt, double max_alt, const double* center, double range,
                 double sun_elevation_deg, double sun_azimuth_deg, float* rays11, float* rays8, void* stream);
 
+/* ---- ECEF bounds of one image's rays: SatelliteDataset.init_scaling_params (datasets/satellite.py:139-151) ---
+ * replaces the host loop that builds every ray of every image with numpy and rpcm and takes the extremes of their near and far points
+ * for scene.loc.  `rpc`, width, height, min_alt, max_alt as for sr_rpc_rays.  Per pixel: sr_rpc_rays' rays8 row, near point = o, far
+ * point = o + far * d in fp32 (separate multiply and add, as the reference's tensor ops :149-150); bounds6 (6 DEVICE floats) = {xmin,
+ * xmax, ymin, ymax, zmin, zmax} over both.  A pixel with a non-finite coordinate contributes to no bound and adds 1 to *n_bad (1 DEVICE
+ * int64); with no finite pixel the bounds are +inf / -inf.  Integer atomics on order-preserving keys: bitwise repeatable.  No host
+ * synchronisation: capturable. */
+int sr_rpc_scene_bounds(const double* rpc, int width, int height, double min_alt, double max_alt, float* bounds6, int64_t* n_bad,
+                        void* stream);
+
 /* ---- depth supervision from tie points: SatelliteDataset_depth (datasets/satellite_depth.py:51-129) ---------
  * `rpc` = 90 HOST doubles as for sr_rpc_rays (the full-resolution camera); colrow = n (col, row) DEVICE fp64 pairs (the JSON's
  * keypoints.2d_coordinates); pts3d = n_pts x 3 DEVICE fp64 ECEF tie points (pts3d.npy); pts3d_idx = n DEVICE int64 rows of pts3d

@@ -106,6 +106,7 @@ SIGNATURES = {
     "sr_sample_pdf_merge": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp]),
     "sr_sample_pdf": (_i, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp]),
     "sr_rpc_rays": (_i, [_vp, _i, _i, _d, _d, _vp, _d, _d, _d, _vp, _vp, _vp]),
+    "sr_rpc_scene_bounds": (_i, [_vp, _i, _i, _d, _d, _vp, _vp, _vp]),
     "sr_rpc_rays_at": (_i, [_vp, _vp, _i64, _d, _d, _vp, _d, _d, _d, _vp, _vp]),
     "sr_reprojection_errors": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sr_keypoint_weights_scratch": (_i, [_i64, _i, C.POINTER(_i64)]),

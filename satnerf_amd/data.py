@@ -9,6 +9,8 @@ the last short batch dropped (``drop_last``) or kept.  Ranks draw disjoint strid
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 
@@ -162,19 +164,185 @@ def read_scene_loc(root_dir):
     """(center (3,) fp32 tensor, scene_range float) from ``root_dir/scene.loc`` as ``SatelliteDataset.__init__`` loads them
     (datasets/satellite.py:108-110): both rounded to fp32 (``scene_range`` is the fp32 maximum of the three scales, returned as a
     Python float of that value).  The file is required: the reference writes it in ``init_scaling_params``, which cannot serialise
-    its own float32 values, and this project does not create it."""
+    its own float32 values; here ``init_scaling_params(root_dir)`` writes it, and only when asked to."""
     import json
     import os
 
     path = os.path.join(root_dir, "scene.loc")
     if not os.path.exists(path):
         raise FileNotFoundError(f"Could not find {path}: the scene's normalisation (X/Y/Z_offset and X/Y/Z_scale of the ECEF bounds) is "
-                                "required; write it with the scene's dataset tools (it is not computed here)")
+                                "required; write it with the scene's dataset tools or data.init_scaling_params (it is not computed here)")
     with open(path) as f:
         d = json.load(f)
     center = torch.tensor([float(d["X_offset"]), float(d["Y_offset"]), float(d["Z_offset"])])
     scene_range = torch.max(torch.tensor([float(d["X_scale"]), float(d["Y_scale"]), float(d["Z_scale"])]))
     return center, float(scene_range)
+
+
+def scene_bounds(images, img_downscale=1.0, device="cuda", names=None, return_per_image=False):
+    """The scene normalisation ``SatelliteDataset.init_scaling_params`` computes (datasets/satellite.py:135-156), on the GPU.
+
+    ``images``: the per-image JSON dicts (``rpc`` in rpcm format, ``height``, ``width``, ``min_alt``, ``max_alt``); per image the grid
+    is ``int(height // s) x int(width // s)`` under ``rescale_rpc(rpc, 1 / s)`` (:142-146), and one ``sr_rpc_scene_bounds`` launch
+    writes the ECEF bounds of its rays' near and far points into its row of an (n_images, 6) table; the host reads that table and the
+    per-image counts of non-finite pixels back in one copy.  An image whose down-scaled grid is empty adds no point, as the
+    reference's meshgrid yields no ray for it.  The scene's extremes then go through ``sat_utils.rpc_scaling_params`` in float32
+    (sat_utils.py:30-37): scale = (max - min) / 2, offset = min + scale.  Returns {"X_scale", "X_offset", "Y_scale", "Y_offset",
+    "Z_scale", "Z_offset"} as Python floats holding those fp32 values; with ``return_per_image`` also the (n_images, 6) fp32 numpy
+    table [xmin, xmax, ymin, ymax, zmin, zmax] (+inf / -inf in the row of an empty image).  An image with a non-finite pixel raises
+    ``ValueError`` naming it (``names``: per-image labels, e.g. the JSON paths) and its count ``n_bad``."""
+    import numpy as np
+
+    from . import ops
+
+    n_img = len(images)
+    if n_img < 1:
+        raise ValueError("no images")
+    dev = torch.device(device)
+    s = float(img_downscale)
+    # one buffer, so one copy back: 6 fp32 bounds per image, then one int64 count per image (6 n int32 words is a multiple of 8 bytes)
+    host = torch.zeros(8 * n_img, dtype=torch.int32)
+    host[:6 * n_img].view(torch.float32).view(n_img, 6).copy_(torch.tensor([math.inf, -math.inf] * 3))
+    raw = host.to(dev)
+    bounds, n_bad = raw[:6 * n_img].view(torch.float32).view(n_img, 6), raw[6 * n_img:].view(torch.int64)
+    sizes = []
+    for k, d in enumerate(images):
+        h, w = int(d["height"] // s), int(d["width"] // s)
+        sizes.append(h * w)
+        if h < 1 or w < 1:
+            continue  # an empty grid: no ray, and no launch (the ABI wants at least one pixel)
+        ops.rpc_scene_bounds(rescale_rpc(d["rpc"], 1.0 / s), w, h, float(d["min_alt"]), float(d["max_alt"]), dev, out=bounds[k],
+                             n_bad=n_bad[k:k + 1])
+    host = raw.cpu()  # the one device-to-host copy
+    per_image = host[:6 * n_img].view(torch.float32).view(n_img, 6).numpy()
+    bad = host[6 * n_img:].view(torch.int64).numpy()
+    for k in range(n_img):
+        if bad[k] > 0:
+            name = names[k] if names is not None else f"image {k}"
+            raise ValueError(f"{name}: n_bad = {int(bad[k])} of its {sizes[k]} pixels have a non-finite ray (RPC localisation or ECEF "
+                             "point); scene bounds are undefined")
+    lo, hi = per_image[:, 0::2].min(0), per_image[:, 1::2].max(0)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError(f"no pixels: every image's grid is empty at img_downscale {img_downscale}")
+    out = {}
+    for a, axis in enumerate("XYZ"):
+        scale = (np.float32(hi[a]) - np.float32(lo[a])) / 2
+        offset = np.float32(lo[a]) + scale
+        out[axis + "_scale"], out[axis + "_offset"] = float(np.float32(scale)), float(np.float32(offset))
+    return (out, per_image) if return_per_image else out
+
+
+def init_scaling_params(root_dir, img_downscale=1.0, device="cuda", overwrite=False):
+    """Write ``root_dir/scene.loc`` from the RPC cameras of every ``*.json`` under ``root_dir``, as ``SatelliteDataset.
+    init_scaling_params`` is meant to (datasets/satellite.py:135-158; the reference's own ``json.dump`` refuses its float32 values):
+    ``scene_bounds`` of those images, written with ``json.dump(..., indent=2)`` under the reference's six keys.  Returns what
+    ``read_scene_loc(root_dir)`` returns.  ``FileExistsError`` if the file exists and ``overwrite`` is false; a JSON without an "rpc"
+    field raises ``ValueError`` naming it."""
+    import glob
+    import json
+    import os
+
+    path = os.path.join(root_dir, "scene.loc")
+    if os.path.exists(path) and not overwrite:
+        raise FileExistsError(f"{path} exists (pass overwrite=True to replace it)")
+    files = sorted(glob.glob("{}/*.json".format(root_dir)))
+    if not files:
+        raise FileNotFoundError(f"no *.json under {root_dir}")
+    images = []
+    for p in files:
+        with open(p) as f:
+            d = json.load(f)
+        if not isinstance(d, dict) or "rpc" not in d:
+            raise ValueError("No 'rpc' field was found in {}".format(p))
+        images.append(d)
+    loc = scene_bounds(images, img_downscale=img_downscale, device=device, names=files)
+    with open(path, "w") as f:
+        json.dump({k: loc[k] for k in ("X_scale", "X_offset", "Y_scale", "Y_offset", "Z_scale", "Z_offset")}, f, indent=2)
+    return read_scene_loc(root_dir)
+
+
+def _split_files(root_dir, name):
+    import os
+
+    with open(os.path.join(root_dir, name)) as f:
+        return [os.path.join(root_dir, line.strip()) for line in f.read().split("\n") if line.strip()]
+
+
+def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_dir=None, create_scene_loc=False):
+    """The rays ``SatelliteDataset(root_dir, img_dir, split, img_downscale, cache_dir)`` builds from a dataset directory, on the GPU.
+
+    ``"train"`` (``load_train_split`` / ``load_data``, datasets/satellite.py:117-121, 160-216): returns (all_rays (N, 11) fp32 -- one
+    preallocated tensor the images' blocks are written into --, all_ids (N,) int64 = the image's line in ``train.txt``, blank lines
+    skipped, and a list of per-image (name, h, w, row_offset)).  ``"val"`` (``load_val_split``, :123-133): a list of per-image dicts
+    {rays (h*w, 11), ts, src_id, h, w}: the first training image with ts 0, then the ``test.txt`` images with ts n_train + k;
+    ``src_id`` is the file id of the JSON's "img".
+
+    Rays come from ``sr_rpc_rays``.  With ``cache_dir`` an existing ``<cache_dir>/<img_id>.data`` is read through ``rays_from_cache``
+    and a missing one is written (:185-196).  ``scene.loc`` is read with ``read_scene_loc``; when it is missing and
+    ``create_scene_loc`` is true, ``init_scaling_params(root_dir, img_downscale)`` writes it first.
+
+    Colours are the caller's: image block k of the training split is rows ``row_offset .. row_offset + h * w`` in row-major pixel order
+    (row ``i // w``, column ``i % w`` of the image resized to h x w), so ``rgbs[row_offset:row_offset + h * w] = image.reshape(h * w,
+    3)`` lines an (N, 3) colour tensor up with ``all_rays`` for ``RayBank(all_rays, rgbs, all_ids, batch_size)``."""
+    import json
+    import os
+
+    from . import ops
+
+    if split not in ("train", "val"):
+        raise ValueError(f"split must be 'train' or 'val', got {split!r}")
+    if create_scene_loc and not os.path.exists(os.path.join(root_dir, "scene.loc")):
+        init_scaling_params(root_dir, img_downscale, device=device)
+    center, scene_range = read_scene_loc(root_dir)
+    train = _split_files(root_dir, "train.txt")
+    if split == "train":
+        files, ids = train, list(range(len(train)))
+    else:
+        if not train:
+            raise ValueError("train.txt lists no image")
+        test = _split_files(root_dir, "test.txt")
+        files, ids = [train[0]] + test, [0] + [len(train) + k for k in range(len(test))]
+    metas = []
+    for p in files:
+        with open(p) as f:
+            d = json.load(f)
+        if "rpc" not in d:
+            raise ValueError("No 'rpc' field was found in {}".format(p))
+        metas.append((d, int(d["height"] // img_downscale), int(d["width"] // img_downscale)))
+    dev = torch.device(device)
+    s = float(img_downscale)
+
+    def block(d, h, w, out):
+        """One image's (h*w, 11) rays into ``out``."""
+        img_id = os.path.splitext(os.path.basename(d["img"]))[0]
+        cache_path = None if cache_dir is None else "{}/{}.data".format(cache_dir, img_id)
+        if cache_path is not None and os.path.exists(cache_path):
+            rays = rays_from_cache(cache_path, center, scene_range, float(d["sun_elevation"]), float(d["sun_azimuth"]))
+            if rays.shape[0] != h * w:
+                raise ValueError(f"{cache_path} holds {rays.shape[0]} rays but the image is {h} x {w} at img_downscale {img_downscale}")
+            out.copy_(rays)
+        elif h * w:
+            _, cache = ops.rpc_rays(rescale_rpc(d["rpc"], 1.0 / s), w, h, float(d["min_alt"]), float(d["max_alt"]), center, scene_range,
+                                    float(d["sun_elevation"]), float(d["sun_azimuth"]), dev, want_cache=cache_path is not None, out=out)
+            if cache_path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(cache_path)), exist_ok=True)
+                torch.save(cache.cpu(), cache_path)
+        return img_id
+
+    if split == "train":
+        counts = [h * w for _, h, w in metas]
+        all_rays = torch.empty(sum(counts), 11, dtype=torch.float32, device=dev)
+        all_ids = torch.repeat_interleave(torch.tensor(ids, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64)).to(dev)
+        index, off = [], 0
+        for (d, h, w), n in zip(metas, counts):
+            index.append((block(d, h, w, all_rays[off:off + n]), h, w, off))
+            off += n
+        return all_rays, all_ids, index
+    out = []
+    for (d, h, w), t in zip(metas, ids):
+        rays = torch.empty(h * w, 11, dtype=torch.float32, device=dev)
+        out.append({"rays": rays, "ts": t, "src_id": block(d, h, w, rays), "h": h, "w": w})
+    return out
 
 
 def depth_supervision_from_keypoints(images, tie_points, center, scene_range, device="cuda", return_point_weights=False, names=None):

@@ -369,28 +369,39 @@ RPC_KEYS = ("row_num", "row_den", "col_num", "col_den")
 RPC_SCALARS = ("row_offset", "col_offset", "lat_offset", "lon_offset", "alt_offset", "row_scale", "col_scale", "lat_scale", "lon_scale", "alt_scale")
 
 
-def rpc_rays(rpc, width, height, min_alt, max_alt, center, scene_range, sun_elevation_deg, sun_azimuth_deg, device, want_cache=False):
+def rpc_rays(rpc, width, height, min_alt, max_alt, center, scene_range, sun_elevation_deg, sun_azimuth_deg, device, want_cache=False,
+             out=None):
     """RPC ray generation of one image on the GPU (sr_rpc_rays): ``rpc`` = dict in rpcm's "rpcm" format (20-term lists row_num,
-    row_den, col_num, col_den + the ten offsets / scales).  Returns (rays (H*W, 11) fp32, cache (H*W, 8) fp32 or None)."""
-    import ctypes
-
-    vals = []
-    for k in RPC_KEYS:
-        c = [float(v) for v in rpc[k]]
-        if len(c) != 20:
-            raise ValueError(f"rpc[{k!r}] must hold the 20 RPC00B coefficients, got {len(c)}")
-        vals += c
-    vals += [float(rpc[k]) for k in RPC_SCALARS]
-    buf = (ctypes.c_double * 90)(*vals)
-    ctr = (ctypes.c_double * 3)(*[float(v) for v in center])
+    row_den, col_num, col_den + the ten offsets / scales).  Returns (rays (H*W, 11) fp32, cache (H*W, 8) fp32 or None); ``out`` = a
+    contiguous (H*W, 11) fp32 tensor on ``device`` to write the rays into (e.g. one image's rows of a dataset's ray tensor)."""
+    buf = rpc_buffer(rpc)
+    ctr = (C.c_double * 3)(*[float(v) for v in center])
     n = int(width) * int(height)
     dev = torch.device(device)
     with torch.cuda.device(dev):
-        rays = torch.empty(n, 11, dtype=torch.float32, device=dev)
+        rays = torch.empty(n, 11, dtype=torch.float32, device=dev) if out is None else _chk(out, "out")
+        if tuple(rays.shape) != (n, 11):
+            raise ValueError(f"out must be ({n}, 11), got {tuple(rays.shape)}")
         cache = torch.empty(n, 8, dtype=torch.float32, device=dev) if want_cache else None
-        _lib.call("sr_rpc_rays", ctypes.addressof(buf), int(width), int(height), float(min_alt), float(max_alt), ctypes.addressof(ctr),
+        _lib.call("sr_rpc_rays", C.addressof(buf), int(width), int(height), float(min_alt), float(max_alt), C.addressof(ctr),
                   float(scene_range), float(sun_elevation_deg), float(sun_azimuth_deg), _p(rays), _p(cache), _stream())
     return rays, cache
+
+
+def rpc_scene_bounds(rpc, width, height, min_alt, max_alt, device, out=None, n_bad=None):
+    """sr_rpc_scene_bounds: the ECEF bounds of one image's rays, near and far points.  Returns (bounds (6,) fp32 = [xmin, xmax, ymin,
+    ymax, zmin, zmax], n_bad int64 with one element = the pixels with a non-finite coordinate, which count in no bound) on ``device``;
+    ``out`` / ``n_bad`` = tensors of that size to write into (e.g. row k of a per-image table).  Nothing is read back."""
+    buf = rpc_buffer(rpc)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        out = torch.empty(6, dtype=torch.float32, device=dev) if out is None else _chk(out, "out")
+        n_bad = torch.empty(1, dtype=torch.int64, device=dev) if n_bad is None else _chk(n_bad, "n_bad", torch.int64)
+        if out.numel() != 6 or n_bad.numel() != 1:
+            raise ValueError(f"out must hold 6 floats and n_bad one int64, got {tuple(out.shape)} and {tuple(n_bad.shape)}")
+        _lib.call("sr_rpc_scene_bounds", C.addressof(buf), int(width), int(height), float(min_alt), float(max_alt), _p(out), _p(n_bad),
+                  _stream())
+    return out, n_bad
 
 
 def rpc_buffer(rpc):
