@@ -473,6 +473,29 @@ int sr_dsm_rasterize(const double* east, const double* north, const double* alt,
                      double resolution, int xsize, int ysize, int radius, double sigma, uint64_t* acc, float* dsm, float* weight,
                      void* stream);
 
+/* ---- cloud fusion: eval_s2p.project_cloud_into_utm_grid (eval_s2p.py:175-226) ---------------------------------
+ * sr_cloud_grid bins a UTM cloud (east / north / alt (N,) DEVICE fp64, sr_depth_to_utm's outputs) into a map_h x map_w grid and keeps
+ * per cell the min (mode 0), max (1), mean (2) or median (3) of the altitudes that landed in it: out (map_h, map_w) DEVICE fp64, NaN
+ * where no point landed, count (map_h, map_w) DEVICE int32.
+ * rule 0 (nearest, the reference's): col = rint((east - x0) / definition), row = rint((north - y0) / definition) in IEEE fp64 with
+ * round-half-to-even (np.round), kept when 0 <= col < map_w and 0 <= row < map_h (-0 is column 0), written to output row
+ * map_h - 1 - row (the reference's flipud: row 0 is north); (x0, y0) = (bb[0], bb[2]).
+ * rule 1 (floor, sr_dsm_rasterize's cell): col = floor((east - x0) / definition), row = floor((y0 - north) / definition), (x0, y0) =
+ * (xoff, yoff) of the DSM grid, output row = row.
+ * Departure: a point whose east, north or alt is not finite contributes nothing (the reference lets a NaN altitude poison avg / med).
+ * Stages, all on `stream` with no host round trip: (1) cell key per point + 32-bit integer histogram, (2) exclusive scan (block sums,
+ * their scan, add), (3) scatter into per-cell segments by an integer cursor, (4) in-place sort of every segment on an order-preserving
+ * 64-bit key (one wave up to 64 keys, one workgroup beyond), (5) reduce: min = first, max = last, med = the middle key or (a + b) / 2
+ * of the two middle ones (np.median bit for bit), avg = the ascending fp64 sum / count.  Every mode reads the sorted segment and no
+ * float atomic is used: the result is bitwise independent of point and arrival order, avg included.
+ * scratch: caller-owned DEVICE bytes (8-byte aligned), at least sr_cloud_grid_scratch(n, map_w, map_h) (HOST only); it need not be
+ * initialised.  stages = 0 runs everything; 1..4 stops after that stage (timing only: out is then not written).  n and map_w * map_h
+ * must each be <= 2^31 - 4096 (int32 offsets), else an error is returned. */
+int sr_cloud_grid_scratch(int64_t n, int map_w, int map_h, int64_t* bytes);
+int sr_cloud_grid(const double* east, const double* north, const double* alt, int64_t n, double x0, double y0, double definition,
+                  int map_w, int map_h, int rule, int mode, void* scratch, int64_t scratch_bytes, double* out, int* count, int stages,
+                  void* stream);
+
 /* ---- DSM registration: dsmr.compute_shift / dsmr.apply_shift (dsmr.py:6-148,163-215), the XY + Z
  * registration of sat_utils.dsm_pointwise_diff (sat_utils.py:172-177) --------------------------------------------------------------
  * u (hu, wu) is the reference DSM (the ground truth), v (hv, wv) the secondary (the prediction): row-major DEVICE fp64 (exact

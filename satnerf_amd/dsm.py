@@ -4,7 +4,8 @@ The reference leaves the GPU here and calls pyproj / utm (``sat_utils.utm_from_l
 (``SatelliteDataset.get_dsm_from_nerf_prediction``) and GDAL / rasterio (``sat_utils.dsm_pointwise_diff``).  This module keeps
 their names and argument order; geometry is fp64, the rasteriser is the HIP kernel of csrc/dsm.hip.  No file I/O: GeoTIFF reading
 and writing stay with the caller (``DSM.transform`` is the affine the reference writes).  The reference's dsmr registration
-(``compute_shift`` / ``apply_shift``, numba on the CPU there) is the HIP search of csrc/dsm_register.hip.
+(``compute_shift`` / ``apply_shift``, numba on the CPU there) is the HIP search of csrc/dsm_register.hip.  Several clouds fuse into
+one DSM by a per-cell median / mean / min / max (``eval_s2p.project_cloud_into_utm_grid``; csrc/cloud_grid.hip, section 7.6).
 
 The rasteriser follows this project's own grid / splat convention (include/satrender.h, sr_dsm_rasterize).  plyflatten cannot be
 run here, so parity with it is not claimed.
@@ -249,6 +250,104 @@ def _dsm_mae_xyz(pred, gt, gt_mask):
     mae = torch.nanmean(err.abs().double())
     transform = _coefs(out)  # raises if the registration is undefined
     return mae.item(), err, rdsm, transform
+
+
+# ---- cloud fusion ------------------------------------------------------------------------------------------
+CLOUD_MODES = ("min", "max", "avg", "med")
+
+
+def _check_mode(mode):
+    if mode not in CLOUD_MODES:
+        raise ValueError(f"mode must be one of {CLOUD_MODES}, got {mode!r}")
+
+
+def project_cloud_into_utm_grid(xyz, bb, definition, mode, mask=None):
+    """``eval_s2p.project_cloud_into_utm_grid`` (eval_s2p.py:175-226) on the GPU: the (map_h, map_w) fp64 device raster whose cell holds
+    the ``mode`` ("min", "max", "avg" or "med") of the altitudes of the points that round to it, NaN where none did, already flipped
+    so that row 0 is north.  ``xyz`` is an (N, >=3) device tensor (east, north, alt), widened to fp64; ``bb`` = [xmin, xmax, ymin,
+    ymax]; map_w = int(round((xmax - xmin) / definition)) + 1 and map_h likewise.  ``mask`` is accepted and ignored: the reference
+    assigns it and never reads it.  Departures: a ``mode`` outside the four raises ValueError (the reference silently takes the
+    "med" branch), and a point with a non-finite coordinate or altitude contributes nothing.  min / max / med equal the reference's
+    bit for bit; every mode is independent of point order."""
+    _check_mode(mode)
+    if not (torch.is_tensor(xyz) and xyz.is_cuda):
+        raise ValueError("xyz must be a GPU tensor: satnerf_amd has no CPU path")
+    if xyz.dim() != 2 or xyz.shape[1] < 3:
+        raise ValueError(f"xyz must be (N, >=3), got {tuple(xyz.shape)}")
+    bb = [float(v) for v in bb]
+    if len(bb) != 4:
+        raise ValueError(f"bb must hold [xmin, xmax, ymin, ymax], got {len(bb)} values")
+    definition = float(definition)
+    map_w = int(round((bb[1] - bb[0]) / definition)) + 1
+    map_h = int(round((bb[3] - bb[2]) / definition)) + 1
+    cols = xyz[:, :3].to(torch.float64).t().contiguous()
+    out, _ = ops.cloud_grid(cols[0], cols[1], cols[2], bb[0], bb[2], definition, map_w, map_h, rule="nearest", mode=mode)
+    return out
+
+
+def _cat(x, name):
+    parts = list(x) if isinstance(x, (list, tuple)) else [x]
+    for t in parts:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f"{name} must be a GPU tensor or a list of GPU tensors: satnerf_amd has no CPU path")
+    if not parts:
+        raise ValueError(f"{name} is an empty list")
+    parts = [t.reshape(-1).to(torch.float64) for t in parts]
+    return parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
+
+
+def dsm_from_clouds(east, north, alt, roi=None, resolution=0.5, mode="med", zone=""):
+    """Fuse UTM clouds into one :class:`DSM` by the per-cell ``mode`` of their altitudes (csrc/cloud_grid.hip) on the DSM grid of
+    :func:`dsm_from_depth`: cell (j, c) = (floor((yoff - north) / r), floor((east - xoff) / r)).  ``east`` / ``north`` / ``alt`` are
+    each a device tensor or a list of device tensors (one per cloud, concatenated); ``roi`` / ``resolution`` size the grid exactly as
+    dsm_from_depth does.  ``dsm`` is fp32 (the median / mean / min / max taken in fp64), ``weight`` the points per cell as fp32.  Points
+    that are not finite, or outside the grid, contribute nothing; the raster is bitwise independent of point and cloud order."""
+    _check_mode(mode)
+    east, north, alt = _cat(east, "east"), _cat(north, "north"), _cat(alt, "alt")
+    if not east.shape == north.shape == alt.shape:
+        raise ValueError(f"east / north / alt must hold one value per point each, got {east.numel()}, {north.numel()}, {alt.numel()}")
+    if roi is not None:
+        xoff, yoff, xsize, ysize, resolution = grid_from_roi(roi)
+        if xsize < 1 or resolution <= 0:
+            raise ValueError(f"zero-size DSM grid from roi {list(roi)}")
+    else:
+        if east.numel() == 0:
+            raise ValueError("no points: the DSM grid cannot be sized without a roi")
+        xmin, xmax, ymin, ymax = ops.dsm_bounds(east, north, alt).cpu().tolist()
+        if not all(math.isfinite(v) for v in (xmin, xmax, ymin, ymax)):
+            raise ValueError("zero-size DSM grid: no usable point")
+        xoff, yoff, xsize, ysize = grid_from_bounds(xmin, xmax, ymin, ymax, resolution)
+    out, count = ops.cloud_grid(east, north, alt, xoff, yoff, resolution, xsize, ysize, rule="floor", mode=mode)
+    return DSM(out.float(), count.float(), float(xoff), float(yoff), float(resolution), str(zone),
+               None if roi is None else tuple(float(v) for v in roi))
+
+
+def render_fused_dsm(models, views, args, center, scene_range, mode="med", **dsm_kwargs):
+    """Render every view and fuse the clouds into one DSM: per ``(rays, ts)`` of ``views``, ``render_image_outputs(...)["depth"]`` ->
+    ``ops.depth_to_utm`` -> :func:`dsm_from_clouds` (``dsm_kwargs``: roi, resolution).  The UTM zone is the first view's first
+    point's and is handed to every later view, so a scene on a zone edge never mixes projections.  With ``roi=`` the result feeds
+    :func:`dsm_mae` unchanged."""
+    from .rendering import render_image_outputs
+
+    _check_mode(mode)
+    views = list(views)
+    if not views:
+        raise ValueError("no views")
+    clouds, number, zone_str = [], 0, ""
+    for rays, ts in views:
+        if not (torch.is_tensor(rays) and rays.is_cuda):
+            raise ValueError("rays must be GPU tensors: satnerf_amd has no CPU path")
+        with torch.no_grad():
+            depth = render_image_outputs(models, rays, ts, args)["depth"]
+        rays32 = rays if rays.dtype == torch.float32 and rays.stride(-1) == 1 else rays.float().contiguous()
+        east, north, alt, zone_out = ops.depth_to_utm(rays32, depth.reshape(-1).float().contiguous(), center, scene_range, number)
+        if not number:
+            meta = zone_out.cpu().tolist()
+            if meta[0] == 0:
+                raise ValueError("the first view's first point is not finite or lies outside latitudes [-80, 84]")
+            number, zone_str = meta[0], zone_string(meta[0], chr(meta[1]) if meta[1] else "")
+        clouds.append((east, north, alt))
+    return dsm_from_clouds([c[0] for c in clouds], [c[1] for c in clouds], [c[2] for c in clouds], mode=mode, zone=zone_str, **dsm_kwargs)
 
 
 def render_dsm(models, rays, ts, args, center, scene_range, **dsm_kwargs):

@@ -863,6 +863,46 @@ def dsm_rasterize(east, north, alt, xoff, yoff, resolution, xsize, ysize, radius
     return dsm, weight
 
 
+# ---- cloud fusion (csrc/cloud_grid.hip) --------------------------------------------------------------------------------------------
+CLOUD_RULES = {"nearest": 0, "floor": 1}
+CLOUD_MODES = {"min": 0, "max": 1, "avg": 2, "med": 3}
+
+
+def cloud_grid_scratch(n, map_w, map_h):
+    """Bytes of scratch sr_cloud_grid needs for n points on a map_h x map_w grid (host only)."""
+    nbytes = C.c_int64(0)
+    _lib.call("sr_cloud_grid_scratch", int(n), int(map_w), int(map_h), C.byref(nbytes))
+    return nbytes.value
+
+
+def cloud_grid(east, north, alt, x0, y0, definition, map_w, map_h, rule="nearest", mode="med", scratch=None, out=None, count=None,
+               stages=0):
+    """(out, count): the (map_h, map_w) fp64 raster of the per-cell ``mode`` ("min" / "max" / "avg" / "med") of the altitudes of the
+    (N,) fp64 device cloud east / north / alt (NaN where no point landed) and the int32 points per cell (sr_cloud_grid).  ``rule``
+    "nearest" is eval_s2p.project_cloud_into_utm_grid's cell with (x0, y0) = (bb[0], bb[2]), "floor" the DSM grid's with (x0, y0) =
+    (xoff, yoff).  ``scratch``: a contiguous device tensor of at least cloud_grid_scratch bytes.  Nothing is read back."""
+    east, north, alt = (_chk(t, k, torch.float64) for t, k in ((east, "east"), (north, "north"), (alt, "alt")))
+    if not (east.dim() == 1 and east.shape == north.shape == alt.shape):
+        raise ValueError("east / north / alt must be three (N,) tensors")
+    if rule not in CLOUD_RULES:
+        raise ValueError(f"rule must be one of {sorted(CLOUD_RULES)}, got {rule!r}")
+    if mode not in CLOUD_MODES:
+        raise ValueError(f"mode must be one of {sorted(CLOUD_MODES)}, got {mode!r}")
+    map_w, map_h = int(map_w), int(map_h)
+    if map_w < 1 or map_h < 1:
+        raise ValueError(f"empty grid ({map_h} x {map_w})")
+    dev = east.device
+    scratch = _metric_scratch(scratch, cloud_grid_scratch(east.shape[0], map_w, map_h), dev)
+    out = torch.empty(map_h, map_w, dtype=torch.float64, device=dev) if out is None else _chk(out, "out", torch.float64)
+    count = torch.empty(map_h, map_w, dtype=torch.int32, device=dev) if count is None else _chk(count, "count", torch.int32)
+    if out.shape != (map_h, map_w) or count.shape != (map_h, map_w):
+        raise ValueError(f"out / count must be ({map_h}, {map_w})")
+    _lib.call("sr_cloud_grid", _p(east), _p(north), _p(alt), east.shape[0], float(x0), float(y0), float(definition), map_w, map_h,
+              CLOUD_RULES[rule], CLOUD_MODES[mode], _p(scratch), scratch.numel() * scratch.element_size(), _p(out), _p(count), int(stages),
+              _stream())
+    return out, count
+
+
 # ---- DSM registration (csrc/dsm_register.hip) --------------------------------------------------------------------------------------
 def _raster(t, name):
     t = _chk(t, name, torch.float64)
