@@ -543,6 +543,20 @@ int sr_image_sse(const float* pred, const float* gt, int64_t n, const uint8_t* m
 int sr_ssim_sum(const float* img1, const float* img2, int64_t planes, int h, int w, void* scratch, int64_t scratch_bytes, double* out,
                 void* stream);
 
+/* ---- a dataset's colours: load_tensor_from_rgb_geotiff (datasets/satellite.py:67-80) from the 8-bit image ------
+ * src: DEVICE bytes of a 3-channel (src_h, src_w) image addressed as src[r * row_stride + c * pix_stride + k * chan_stride] (strides in
+ * bytes, all >= 1: a dense HWC image is (3 w, 3, 1), a dense CHW image (w, 1, h w)); out: (out_h * out_w, 3) fp32 DEVICE rows,
+ * out[(r * out_w + c) * 3 + k].  Values are v = (float)u8 / 255.0f, which is the reference's float32(float64(u8) / 255.) for all 256 bytes.
+ * out_h == src_h and out_w == src_w: the plain conversion.  Any other size: torchvision's tensor Resize(BICUBIC) = ATen's
+ * upsample_bicubic2d with align_corners=False and no antialias, all in fp32 with every product and sum rounded (no fma).  Per axis:
+ * scale = (float)n_in / (float)n_out, src = scale * ((float)dst + 0.5f) - 0.5f, i0 = floorf(src), t = src - i0, taps i0 - 1 .. i0 + 2
+ * clamped to [0, n_in - 1], with the cubic-convolution weights (A = -0.75) w(x) = ((A + 2) x - (A + 3)) x^2 + 1 for |x| <= 1 and
+ * ((A x - 5 A) x + 8 A) x - 4 A for 1 < |x| < 2 at x = t + 1, t, 1 - t, 2 - t.  An output value is the 4 x 4 weighted sum (columns, then
+ * rows) and is not clamped to [0, 1].  Both layouts of one image give the same bits.  out_h * out_w == 0: nothing is launched.  No
+ * scratch and no host synchronisation: capturable. */
+int sr_image_colors(const uint8_t* src, int src_h, int src_w, int64_t row_stride, int64_t pix_stride, int64_t chan_stride, int out_h,
+                    int out_w, float* out, void* stream);
+
 /* ---- training-step kernels --------------------------------------------------------------
  * sr_satnerf_loss: metrics.SatNerfLoss for the coarse model (metrics.py:21-25,56-73): value = sum of
  * loss_parts[0 .. ceil(N/4)), and grad_scale * dLoss/d{rgb (N,3), weights (N,S), beta (N,S)} in g_*.

@@ -129,6 +129,7 @@ SIGNATURES = {
     "sr_image_metrics_scratch": (_i, [_i64, _i64, _i, _i, C.POINTER(_i64)]),
     "sr_image_sse": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sr_ssim_sum": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp]),
+    "sr_image_colors": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
 }
 
 _lib = None

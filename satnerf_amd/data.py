@@ -268,32 +268,14 @@ def _split_files(root_dir, name):
         return [os.path.join(root_dir, line.strip()) for line in f.read().split("\n") if line.strip()]
 
 
-def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_dir=None, create_scene_loc=False):
-    """The rays ``SatelliteDataset(root_dir, img_dir, split, img_downscale, cache_dir)`` builds from a dataset directory, on the GPU.
-
-    ``"train"`` (``load_train_split`` / ``load_data``, datasets/satellite.py:117-121, 160-216): returns (all_rays (N, 11) fp32 -- one
-    preallocated tensor the images' blocks are written into --, all_ids (N,) int64 = the image's line in ``train.txt``, blank lines
-    skipped, and a list of per-image (name, h, w, row_offset)).  ``"val"`` (``load_val_split``, :123-133): a list of per-image dicts
-    {rays (h*w, 11), ts, src_id, h, w}: the first training image with ts 0, then the ``test.txt`` images with ts n_train + k;
-    ``src_id`` is the file id of the JSON's "img".
-
-    Rays come from ``sr_rpc_rays``.  With ``cache_dir`` an existing ``<cache_dir>/<img_id>.data`` is read through ``rays_from_cache``
-    and a missing one is written (:185-196).  ``scene.loc`` is read with ``read_scene_loc``; when it is missing and
-    ``create_scene_loc`` is true, ``init_scaling_params(root_dir, img_downscale)`` writes it first.
-
-    Colours are the caller's: image block k of the training split is rows ``row_offset .. row_offset + h * w`` in row-major pixel order
-    (row ``i // w``, column ``i % w`` of the image resized to h x w), so ``rgbs[row_offset:row_offset + h * w] = image.reshape(h * w,
-    3)`` lines an (N, 3) colour tensor up with ``all_rays`` for ``RayBank(all_rays, rgbs, all_ids, batch_size)``."""
+def _split_images(root_dir, split, img_downscale):
+    """The images of a split in the order ``load_rays`` and ``load_colors`` share: ([(JSON dict, h, w)], ids) with the down-scaled size
+    ``int(height // img_downscale)`` x ``int(width // img_downscale)`` (datasets/satellite.py:191-192).  ``"train"``: the ``train.txt``
+    images, id = the line; ``"val"``: the first training image with id 0, then the ``test.txt`` images with ids n_train + k."""
     import json
-    import os
-
-    from . import ops
 
     if split not in ("train", "val"):
         raise ValueError(f"split must be 'train' or 'val', got {split!r}")
-    if create_scene_loc and not os.path.exists(os.path.join(root_dir, "scene.loc")):
-        init_scaling_params(root_dir, img_downscale, device=device)
-    center, scene_range = read_scene_loc(root_dir)
     train = _split_files(root_dir, "train.txt")
     if split == "train":
         files, ids = train, list(range(len(train)))
@@ -309,6 +291,35 @@ def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_d
         if "rpc" not in d:
             raise ValueError("No 'rpc' field was found in {}".format(p))
         metas.append((d, int(d["height"] // img_downscale), int(d["width"] // img_downscale)))
+    return metas, ids
+
+
+def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_dir=None, create_scene_loc=False):
+    """The rays ``SatelliteDataset(root_dir, img_dir, split, img_downscale, cache_dir)`` builds from a dataset directory, on the GPU.
+
+    ``"train"`` (``load_train_split`` / ``load_data``, datasets/satellite.py:117-121, 160-216): returns (all_rays (N, 11) fp32 -- one
+    preallocated tensor the images' blocks are written into --, all_ids (N,) int64 = the image's line in ``train.txt``, blank lines
+    skipped, and a list of per-image (name, h, w, row_offset)).  ``"val"`` (``load_val_split``, :123-133): a list of per-image dicts
+    {rays (h*w, 11), ts, src_id, h, w}: the first training image with ts 0, then the ``test.txt`` images with ts n_train + k;
+    ``src_id`` is the file id of the JSON's "img".
+
+    Rays come from ``sr_rpc_rays``.  With ``cache_dir`` an existing ``<cache_dir>/<img_id>.data`` is read through ``rays_from_cache``
+    and a missing one is written (:185-196).  ``scene.loc`` is read with ``read_scene_loc``; when it is missing and
+    ``create_scene_loc`` is true, ``init_scaling_params(root_dir, img_downscale)`` writes it first.
+
+    Colours come from ``load_colors`` (or both at once from ``load_dataset``): image block k of the training split is rows ``row_offset ..
+    row_offset + h * w`` in row-major pixel order (row ``i // w``, column ``i % w`` of the image resized to h x w), and ``load_colors``
+    writes the same blocks of an (N, 3) colour tensor for ``RayBank(all_rays, rgbs, all_ids, batch_size)``."""
+    import os
+
+    from . import ops
+
+    if split not in ("train", "val"):
+        raise ValueError(f"split must be 'train' or 'val', got {split!r}")
+    if create_scene_loc and not os.path.exists(os.path.join(root_dir, "scene.loc")):
+        init_scaling_params(root_dir, img_downscale, device=device)
+    center, scene_range = read_scene_loc(root_dir)
+    metas, ids = _split_images(root_dir, split, img_downscale)
     dev = torch.device(device)
     s = float(img_downscale)
 
@@ -343,6 +354,103 @@ def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_d
         rays = torch.empty(h * w, 11, dtype=torch.float32, device=dev)
         out.append({"rays": rays, "ts": t, "src_id": block(d, h, w, rays), "h": h, "w": w})
     return out
+
+
+def colors_from_image(image, h, w, device="cuda", out=None, layout=None):
+    """The (h * w, 3) fp32 colour rows of one 8-bit RGB image on the GPU, as ``load_tensor_from_rgb_geotiff`` (datasets/satellite.py:
+    67-80) makes them: ``u8 / 255``, and the bicubic resize to h x w when that is not the image's own size.
+    ``image``: a uint8 array or tensor, (H, W, 3) or (3, H, W), on the host or already on the device; the host uploads its 3 bytes per
+    pixel and ``ops.image_colors`` does the rest.  ``out``: (h * w, 3) fp32 rows on ``device`` to write into; ``layout``: "hwc" / "chw"
+    for an image whose shape reads both ways."""
+    import contextlib
+
+    import numpy as np
+
+    from . import ops
+
+    t = image if torch.is_tensor(image) else torch.from_numpy(np.require(np.asarray(image), requirements=["C", "W"]))
+    if t.dtype != torch.uint8:
+        raise ValueError(f"image must be uint8 (8-bit colours), got {t.dtype}")
+    dev = torch.device(device)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        return ops.image_colors(t.to(dev).contiguous(), int(h), int(w), out=out, layout=layout)
+
+
+def _read_image_pillow(path):
+    import numpy as np
+    from PIL import Image
+
+    with Image.open(path) as im:
+        return np.asarray(im)
+
+
+def load_colors(root_dir, img_dir, split="train", img_downscale=1.0, device="cuda", reader=None):
+    """The colours ``SatelliteDataset(root_dir, img_dir, split, img_downscale)`` loads (``load_data``, datasets/satellite.py:160-216, through
+    ``load_tensor_from_rgb_geotiff``, :67-80), on the GPU, in the order and sizes of ``load_rays``: image ``os.path.join(img_dir,
+    d["img"])`` of every JSON of the split becomes h * w rows, h = int(height // img_downscale), w = int(width // img_downscale).
+
+    ``"train"``: one (N, 3) fp32 tensor whose block k is rows ``row_offset .. row_offset + h * w`` of ``load_rays``'s index, written in
+    place.  ``"val"``: a list of (h * w, 3) tensors in ``load_rays``'s order.  ``reader(path)`` returns the image as a uint8 array,
+    (H, W, 3) or (3, H, W) (e.g. rasterio's ``f.read()``); the default opens the file with Pillow.  An image that is not 8-bit, does not
+    have exactly three bands, or whose size is not the JSON's ``height`` x ``width`` raises ``ValueError`` naming the file -- the
+    reference would pair such colours with the wrong rays.  An image whose down-scaled grid is empty is still read and checked, and
+    adds no rows."""
+    import os
+
+    import numpy as np
+
+    metas, _ = _split_images(root_dir, split, img_downscale)
+    dev = torch.device(device)
+    read = _read_image_pillow if reader is None else reader
+
+    def block(d, h, w, out):
+        """One image's (h*w, 3) colours into ``out``."""
+        path = os.path.join(img_dir, d["img"])
+        img = np.asarray(read(path))
+        if img.dtype != np.uint8:
+            raise ValueError(f"{path} is not an 8-bit image (its samples are {img.dtype}); 16-bit imagery is not supported")
+        full = (int(d["height"]), int(d["width"]))
+        shape = tuple(img.shape)
+        if shape == full + (3,):
+            layout = "hwc"
+        elif shape == (3,) + full:
+            layout = "chw"
+        elif len(shape) != 3 or 3 not in (shape[0], shape[2]):
+            raise ValueError(f"{path} does not have exactly three bands (its shape is {shape}); colours need an RGB image")
+        else:
+            size = shape[:2] if shape[2] == 3 else shape[1:]
+            raise ValueError(f"{path} is {size[0]} x {size[1]} but its JSON says height x width = {full[0]} x {full[1]}: colours and "
+                             "rays would not line up")
+        if h * w:
+            colors_from_image(img, h, w, dev, out=out, layout=layout)
+
+    if split == "train":
+        counts = [h * w for _, h, w in metas]
+        all_rgbs = torch.empty(sum(counts), 3, dtype=torch.float32, device=dev)
+        off = 0
+        for (d, h, w), n in zip(metas, counts):
+            block(d, h, w, all_rgbs[off:off + n])
+            off += n
+        return all_rgbs
+    out = []
+    for d, h, w in metas:
+        out.append(torch.empty(h * w, 3, dtype=torch.float32, device=dev))
+        block(d, h, w, out[-1])
+    return out
+
+
+def load_dataset(root_dir, img_dir, split="train", img_downscale=1.0, device="cuda", cache_dir=None, create_scene_loc=False, reader=None):
+    """``load_rays`` and ``load_colors`` of one split: what ``SatelliteDataset(root_dir, img_dir, split, img_downscale, cache_dir)`` holds.
+    ``"train"``: (all_rays (N, 11), all_rgbs (N, 3), all_ids (N,), index), ready for ``RayBank(all_rays, all_rgbs, all_ids, batch_size)``;
+    ``"val"``: ``load_rays``'s per-image dicts with ``"rgbs"`` (h * w, 3) added, ready for ``evaluate_image``."""
+    rays = load_rays(root_dir, split, img_downscale, device=device, cache_dir=cache_dir, create_scene_loc=create_scene_loc)
+    rgbs = load_colors(root_dir, img_dir, split, img_downscale, device=device, reader=reader)
+    if split == "train":
+        all_rays, all_ids, index = rays
+        return all_rays, rgbs, all_ids, index
+    for v, c in zip(rays, rgbs):
+        v["rgbs"] = c
+    return rays
 
 
 def depth_supervision_from_keypoints(images, tie_points, center, scene_range, device="cuda", return_point_weights=False, names=None):

@@ -1072,3 +1072,39 @@ def ssim_sum(img1, img2, out=None, scratch=None):
     scratch = _metric_scratch(scratch, image_metrics_scratch(planes=b * c, h=h, w=w), img1.device)
     _lib.call("sr_ssim_sum", _p(img1), _p(img2), b * c, h, w, _p(scratch), scratch.numel() * scratch.element_size(), _p(out), _stream())
     return out
+
+
+# ---- a dataset's colours (csrc/image_colors.hip) ------------------------------------------------------------------------------------
+def image_colors(image_u8, out_h, out_w, out=None, layout=None):
+    """sr_image_colors: the (out_h * out_w, 3) fp32 colour rows of one 8-bit image, ``u8 / 255`` and -- unless (out_h, out_w) is the
+    image's own size -- the bicubic resize of the reference's loader (datasets/satellite.py:67-80).  ``image_u8``: a contiguous uint8
+    device tensor, (H, W, 3) (``layout="hwc"``) or (3, H, W) (``"chw"``); the layout is read off the shape, and a 3 x W x 3 image needs
+    it said.  ``out`` = an (out_h * out_w, 3) fp32 tensor with contiguous rows to write into (e.g. one image's rows of a dataset's
+    colour tensor).  Nothing is launched for an empty output."""
+    image_u8 = _chk(image_u8, "image_u8", torch.uint8)
+    if image_u8.dim() != 3:
+        raise ValueError(f"image_u8 must be (H, W, 3) or (3, H, W), got {tuple(image_u8.shape)}")
+    if layout is None:
+        first, last = image_u8.shape[0] == 3, image_u8.shape[2] == 3
+        if first and last:
+            raise ValueError(f"image_u8 {tuple(image_u8.shape)} reads as (H, W, 3) and as (3, H, W): pass layout='hwc' or layout='chw'")
+        if not (first or last):
+            raise ValueError(f"image_u8 must have three bands, (H, W, 3) or (3, H, W), got {tuple(image_u8.shape)}")
+        layout = "chw" if first else "hwc"
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if image_u8.shape[0 if layout == "chw" else 2] != 3:
+        raise ValueError(f"image_u8 {tuple(image_u8.shape)} does not have three bands in layout {layout!r}")
+    h, w = (image_u8.shape[1], image_u8.shape[2]) if layout == "chw" else (image_u8.shape[0], image_u8.shape[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"image_u8 must be at least 1 x 1, got {h} x {w}")
+    strides = (w, 1, h * w) if layout == "chw" else (3 * w, 3, 1)
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h < 0 or out_w < 0:
+        raise ValueError(f"out_h and out_w must be >= 0, got {out_h} and {out_w}")
+    n = out_h * out_w
+    out = torch.empty(n, 3, dtype=torch.float32, device=image_u8.device) if out is None else _chk(out, "out")
+    if tuple(out.shape) != (n, 3):
+        raise ValueError(f"out must be ({n}, 3), got {tuple(out.shape)}")
+    _lib.call("sr_image_colors", _p(image_u8), h, w, strides[0], strides[1], strides[2], out_h, out_w, _p(out), _stream())
+    return out
