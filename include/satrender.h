@@ -557,6 +557,43 @@ int sr_ssim_sum(const float* img1, const float* img2, int64_t planes, int h, int
 int sr_image_colors(const uint8_t* src, int src_h, int src_w, int64_t row_stride, int64_t pix_stride, int64_t chan_stride, int out_h,
                     int out_w, float* out, void* stream);
 
+/* ---- a Blender scene's colours and rays: BlenderDataset (datasets/blender.py:12-209) after the PNG decode ------
+ * sr_blender_colors: Pillow's 8-bit Image.resize((out_w, out_h), Image.LANCZOS) of one RGBA image, byte for byte, then ToTensor and the
+ * blend onto white.  src: DEVICE bytes of a 4-channel (src_h, src_w) image addressed as src[r * row_stride + c * pix_stride + k *
+ * chan_stride] (strides in bytes, all >= 1: dense HWC is (4 w, 4, 1), dense CHW (w, 1, h w)); both layouts give the same bits.  Sides:
+ * source 1..65536, output 0..65536; out_h * out_w == 0 launches nothing.
+ * Premultiply on load: c' = MULDIV255(c, a): t = c * a + 128, c' = ((t >> 8) + t) >> 8; alpha unchanged.
+ * Coefficients, per axis, built on the HOST in fp64 and passed as DEVICE int32 tables coef (n_out, ksize), rows zero-padded
+ * (coef_w: src_w -> out_w, coef_h: src_h -> out_h; NULL for an axis whose size does not change): scale = n_in / n_out, fs =
+ * max(scale, 1), support = 3 fs, ksize = 2 ceil(support) + 1; for output index xx: center = (xx + 0.5) scale, xmin = max((int)(center -
+ * support + 0.5), 0), xmax = min((int)(center + support + 0.5), n_in) - xmin, w[x] = L((x + xmin - center + 0.5) / fs) for x < xmax, L(x)
+ * = sinc(x) sinc(x / 3) on -3 <= x < 3 and 0 elsewhere, sinc(0) = 1, else sinc(x) = sin(pi x) / (pi x); w is divided by its running sum
+ * taken in index order; k = (int)(w 2^22 + 0.5) for w >= 0, (int)(w 2^22 - 0.5) for w < 0 (truncation toward zero).  xmin and xmax
+ * are recomputed on the device from the same fp64 expressions (clamped to the source and to ksize), so there is no bounds table;
+ * ksize_w / ksize_h must be the ksize above for the sizes given.
+ * Each pass: acc = 2^21 + sum_x pixel[xmin + x] k[x] in int32 per band, output = clamp(acc >> 22, 0, 255) as u8.  Horizontal first,
+ * over the four premultiplied bands, into scratch (src_h, out_w, 4) u8; the vertical pass runs over that.  A pass with n_out == n_in is
+ * skipped; with both skipped the bytes are the source's own (no premultiply round trip).
+ * Un-premultiply (after a pass ran): a == 0 or a == 255 keeps the colour bytes, else c = min(255 c' / a, 255), integer division.
+ * Outputs (DEVICE): rgbs (out_h * out_w, 3) fp32 = v_c v_a + (1.0f - v_a) with v = (float)u8 / 255.0f, every product, difference and sum
+ * rounded, not clamped (datasets/blender.py:139); valid_mask (out_h * out_w) u8 = a > 0, may be NULL; rgba (out_h * out_w, 4) u8, the
+ * resized image, 4-byte aligned, may be NULL.
+ * scratch: caller-owned DEVICE bytes, 4-byte aligned, at least sr_blender_colors_scratch (HOST only; 0 unless both passes run).
+ * stages = 0 runs everything; 1 stops after the horizontal pass when a vertical one follows (timing only: no output is written).
+ * Errors (null pointers with a non-empty output, strides < 1, sides out of range, a ksize that does not fit n_in -> n_out, scratch too
+ * small or misaligned) return before anything touches the device.  No host synchronisation: capturable.
+ * sr_pinhole_rays: get_ray_directions + get_rays + near / far (datasets/blender.py:12-59,142-149): out (h * w, 8) fp32 DEVICE rows
+ * [o (3), d (3), near, far], 16-byte aligned, pixel (r, c) at row r * w + c.  fx, fy, cx, cy, near, far and c2w (HOST, 12 floats, row-major
+ * (3, 4) = [R | o]) are fp32 as the reference's tensors hold them.  Per pixel in fp64, every operation rounded: dx = (c - cx) / fx, dy =
+ * -((r - cy) / fy), dz = -1, w_k = (dx R[k][0] + dy R[k][1]) + dz R[k][2], n = sqrt((w_0^2 + w_1^2) + w_2^2), d_k = w_k / n rounded to
+ * fp32 once; o = c2w[:, 3].  h * w == 0 launches nothing.  No scratch, no host synchronisation: capturable. */
+int sr_blender_colors_scratch(int src_h, int src_w, int out_h, int out_w, int64_t* bytes);
+int sr_blender_colors(const uint8_t* src, int src_h, int src_w, int64_t row_stride, int64_t pix_stride, int64_t chan_stride, int out_h,
+                      int out_w, const int32_t* coef_w, int ksize_w, const int32_t* coef_h, int ksize_h, void* scratch,
+                      int64_t scratch_bytes, float* rgbs, uint8_t* valid_mask, uint8_t* rgba, int stages, void* stream);
+int sr_pinhole_rays(int h, int w, float fx, float fy, float cx, float cy, const float* c2w, float near, float far, float* out,
+                    void* stream);
+
 /* ---- training-step kernels --------------------------------------------------------------
  * sr_satnerf_loss: metrics.SatNerfLoss for the coarse model (metrics.py:21-25,56-73): value = sum of
  * loss_parts[0 .. ceil(N/4)), and grad_scale * dLoss/d{rgb (N,3), weights (N,S), beta (N,S)} in g_*.

@@ -453,6 +453,110 @@ def load_dataset(root_dir, img_dir, split="train", img_downscale=1.0, device="cu
     return rays
 
 
+def blender_colors_from_image(image, h, w, device="cuda", out=None, layout=None):
+    """((h * w, 3) fp32 colours, (h * w,) bool valid_mask) of one 8-bit RGBA image on the GPU, as ``BlenderDataset`` makes them
+    (datasets/blender.py:136-139,179-183): Pillow's Lanczos resize to h x w byte for byte, ``u8 / 255``, the blend onto white and
+    ``alpha > 0``.  ``image``: a uint8 array or tensor, (H, W, 4) or (4, H, W), on the host or already on the
+    device; the host uploads its 4 bytes per pixel and ``ops.blender_colors`` does the rest.  ``out``: (h * w, 3) fp32 rows on ``device``
+    to write the colours into; ``layout``: "hwc" / "chw" for an image whose shape reads both ways."""
+    import contextlib
+
+    import numpy as np
+
+    from . import ops
+
+    t = image if torch.is_tensor(image) else torch.from_numpy(np.require(np.asarray(image), requirements=["C", "W"]))
+    if t.dtype != torch.uint8:
+        raise ValueError(f"image must be uint8 (8-bit RGBA), got {t.dtype}")
+    dev = torch.device(device)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        return ops.blender_colors(t.to(dev).contiguous(), int(h), int(w), out=out, layout=layout)
+
+
+def blender_rays(h, w, focal, c2w, near=2.0, far=6.0, device="cuda", out=None):
+    """The (h * w, 8) fp32 rays [o, d, near, far] of one Blender frame on the GPU: ``get_ray_directions(h, w, K)`` and ``get_rays`` with
+    ``read_meta``'s K (datasets/blender.py:12-59,104-112): fx = fy = focal, cx = w / 2, cy = h / 2.  ``c2w``: the frame's (3, 4)
+    camera-to-world matrix.  ``out``: (h * w, 8) fp32 rows on ``device`` to write into."""
+    import contextlib
+
+    from . import ops
+
+    dev = torch.device(device)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        return ops.pinhole_rays(h, w, focal, focal, w / 2, h / 2, c2w, near, far, out=out)
+
+
+def load_blender(root_dir, split="train", img_wh=(400, 400), device="cuda", reader=None):
+    """What ``BlenderDataset(root_dir, split, img_wh)`` holds (datasets/blender.py:82-209, ``perturbation=[]``), on the GPU.
+
+    Reads ``transforms_{split.split('_')[-1]}.json``; focal = 0.5 * 800 / tan(0.5 * camera_angle_x) * (img_wh[0] / 800) in fp64, near 2,
+    far 6; frame images are ``os.path.join(root_dir, frame["file_path"] + ".png")``, read through ``reader(path)`` -- a uint8 array,
+    (H, W, 4) or (4, H, W) -- or Pillow.  Colours come from ``blender_colors_from_image``, rays from ``blender_rays``.
+
+    ``"train"``: (all_rays (N, 8), all_rgbs (N, 3), all_ts (N,) int64); frame t's block is rows ``t h w .. (t + 1) h w`` in row-major
+    pixel order with ts = t, written in place frame after frame (the reference's ``all_rays[:, :8]``, ``all_rgbs`` and
+    ``all_rays[:, 8].long()``).  Any other split (``"val"``, ``"test"``, ``"test_train"``): a list of the reference's ``__getitem__``
+    dicts {"rays" (h w, 8), "ts" (h w,) int64, "rgbs" (h w, 3), "c2w" (3, 4), "valid_mask" (h w,) bool}, one per frame; ``"val"`` stops
+    after 8 frames (its ``__len__``), and ts is 0 except for ``"test_train"``, where frame idx != 0 gets idx.  An image that is not
+    8-bit or does not have exactly four bands raises ``ValueError`` naming the file (the reference would blend with the blue channel as
+    alpha); so does an ``img_wh`` that is not square (the reference's assert).  The layout is read off the shape: exactly one of the
+    first and last axes must be 4, so a 4 x W x 4 array is refused as ambiguous; an array whose first axis is 4 is taken as (4, H, W)
+    whatever its last axis (a (4, W, 3) array cannot be told from an RGBA image three pixels wide)."""
+    import json
+    import math
+    import os
+
+    import numpy as np
+
+    w, h = int(img_wh[0]), int(img_wh[1])
+    if w != h:
+        raise ValueError(f"img_wh must be square, as the reference requires (got {tuple(img_wh)})")
+    which = split.rsplit("_", 1)[-1]  # "test_train" reads the training frames
+    with open(os.path.join(root_dir, "transforms_" + which + ".json")) as f:
+        meta = json.load(f)
+    focal = (400.0 / math.tan(meta["camera_angle_x"] / 2)) * (w / 800)  # the 800-pixel focal length, then the scale to w, in that order
+    near, far = 2.0, 6.0
+    dev = torch.device(device)
+    read = _read_image_pillow if reader is None else reader
+
+    def block(frame, rays, rgbs):
+        """One frame's rays and colours into ``rays`` and ``rgbs``; returns (c2w, valid_mask)."""
+        c2w = np.array(frame["transform_matrix"], dtype=np.float64)[:3, :4].astype(np.float32)
+        path = os.path.join(root_dir, frame["file_path"] + ".png")
+        img = np.asarray(read(path))
+        if img.dtype != np.uint8:
+            raise ValueError(f"{path} is not an 8-bit image (its samples are {img.dtype}); 16-bit imagery is not supported")
+        first, last = img.ndim == 3 and img.shape[0] == 4, img.ndim == 3 and img.shape[2] == 4
+        if not (first or last):
+            raise ValueError(f"{path} does not have exactly four bands (its shape is {tuple(img.shape)}); the loader needs an RGBA image")
+        if first and last:
+            raise ValueError(f"{path} has shape {tuple(img.shape)}, which reads as (H, W, 4) and as (4, H, W): the loader cannot tell its "
+                             "four bands from a side of four pixels")
+        layout = "chw" if first else "hwc"
+        _, mask = blender_colors_from_image(img, h, w, dev, out=rgbs, layout=layout)
+        blender_rays(h, w, focal, c2w, near, far, dev, out=rays)
+        return c2w, mask
+
+    frames = meta["frames"]
+    n = h * w
+    if split == "train":
+        all_rays = torch.empty(len(frames) * n, 8, dtype=torch.float32, device=dev)
+        all_rgbs = torch.empty(len(frames) * n, 3, dtype=torch.float32, device=dev)
+        for t, frame in enumerate(frames):
+            block(frame, all_rays[t * n:(t + 1) * n], all_rgbs[t * n:(t + 1) * n])
+        all_ts = torch.arange(len(frames), dtype=torch.int64, device=dev).repeat_interleave(n)
+        return all_rays, all_rgbs, all_ts
+    out = []
+    for idx, frame in enumerate(frames[:8] if split == "val" else frames):
+        rays = torch.empty(n, 8, dtype=torch.float32, device=dev)
+        rgbs = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        c2w, mask = block(frame, rays, rgbs)
+        t = idx if split == "test_train" and idx != 0 else 0
+        out.append({"rays": rays, "ts": torch.full((n,), t, dtype=torch.int64, device=dev), "rgbs": rgbs,
+                    "c2w": torch.from_numpy(c2w).to(dev), "valid_mask": mask})
+    return out
+
+
 def depth_supervision_from_keypoints(images, tie_points, center, scene_range, device="cuda", return_point_weights=False, names=None):
     """The depth-supervision data of ``SatelliteDataset_depth.load_depth_data`` (datasets/satellite_depth.py:51-129), on the GPU.
 

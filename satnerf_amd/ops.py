@@ -1,7 +1,8 @@
 """Typed Python wrappers over the C ABI (one function per entry point of include/satrender.h).
 
 Every wrapper validates device / dtype / contiguity (the library itself sees only raw pointers), enqueues on
-torch's current HIP stream and returns torch tensors it allocated.  No arithmetic happens here.
+torch's current HIP stream and returns torch tensors it allocated.  No arithmetic happens here beyond the small host-side tables
+an entry is defined to take (e.g. ``lanczos_tables``).
 """
 from __future__ import annotations
 
@@ -1107,4 +1108,127 @@ def image_colors(image_u8, out_h, out_w, out=None, layout=None):
     if tuple(out.shape) != (n, 3):
         raise ValueError(f"out must be ({n}, 3), got {tuple(out.shape)}")
     _lib.call("sr_image_colors", _p(image_u8), h, w, strides[0], strides[1], strides[2], out_h, out_w, _p(out), _stream())
+    return out
+
+
+# ---- a Blender scene's colours and rays (csrc/blender.hip) ----------------------------------------------------------------------------
+_lanczos_host, _lanczos_dev = {}, {}
+
+
+def lanczos_tables(n_in, n_out):
+    """(bounds (n_out, 2) int32 = [xmin, count], coef (n_out, ksize) int32): Pillow's 8-bit Lanczos coefficients of one axis resized
+    n_in -> n_out, as include/satrender.h defines them (fp64 on the host, 22-bit fixed point, rows zero-padded).  Read-only numpy
+    arrays, cached per (n_in, n_out); ``sr_blender_colors`` takes ``coef`` and recomputes the bounds itself."""
+    import numpy as np
+
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"n_in and n_out must be >= 1, got {n_in} and {n_out}")
+    hit = _lanczos_host.get((n_in, n_out))
+    if hit is not None:
+        return hit
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 3.0 * fs
+    ksize = 2 * int(np.ceil(support)) + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)  # astype truncates toward zero, as a C cast does
+    count = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+    x = np.arange(ksize, dtype=np.float64)[None, :]
+    arg = (x + xmin[:, None] - center[:, None] + 0.5) / fs
+
+    def sinc(v):
+        pv = np.pi * np.where(v == 0.0, 1.0, v)
+        return np.where(v == 0.0, 1.0, np.sin(pv) / pv)
+
+    w = np.where((arg >= -3.0) & (arg < 3.0) & (x < count[:, None]), sinc(arg) * sinc(arg / 3.0), 0.0)
+    total = np.zeros(n_out)
+    for j in range(ksize):  # the running sum in index order (a padded tap adds an exact zero)
+        total = total + w[:, j]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    coef = np.where(w < 0, w * 4194304.0 - 0.5, w * 4194304.0 + 0.5).astype(np.int64).astype(np.int32)
+    bounds = np.stack([xmin, count], 1).astype(np.int32)
+    coef.setflags(write=False), bounds.setflags(write=False)
+    _lanczos_host[(n_in, n_out)] = bounds, coef
+    return bounds, coef
+
+
+def _lanczos_device(n_in, n_out, dev):
+    """The coefficient table of lanczos_tables on ``dev`` (uploaded once per device) and its ksize."""
+    key = (int(n_in), int(n_out), dev.index)
+    t = _lanczos_dev.get(key)
+    if t is None:
+        t = _lanczos_dev[key] = torch.from_numpy(lanczos_tables(n_in, n_out)[1].copy()).to(dev)
+    return t, t.shape[1]
+
+
+def blender_colors_scratch(src_h, src_w, out_h, out_w):
+    """Bytes of scratch sr_blender_colors needs for this resize (host only): the (src_h, out_w, 4) intermediate when both passes run."""
+    nbytes = C.c_int64(0)
+    _lib.call("sr_blender_colors_scratch", int(src_h), int(src_w), int(out_h), int(out_w), C.byref(nbytes))
+    return nbytes.value
+
+
+def blender_colors(image_u8, out_h, out_w, out=None, layout=None, want_rgba=False):
+    """sr_blender_colors: one 8-bit RGBA image resized to (out_h, out_w) as Pillow's ``Image.resize(..., Image.LANCZOS)`` does, byte for
+    byte, and blended onto white as the reference's BlenderDataset does (datasets/blender.py:136-139).  ``image_u8``: a contiguous uint8
+    device tensor, (H, W, 4) (``layout="hwc"``) or (4, H, W) (``"chw"``); the layout is read off the shape, and a 4 x W x 4 image needs it
+    said.  Returns (rgbs (out_h * out_w, 3) fp32, valid_mask (out_h * out_w,) bool = alpha > 0), and with ``want_rgba`` also the resized
+    image, (out_h, out_w, 4) uint8.  ``out`` = an (out_h * out_w, 3) fp32 tensor with contiguous rows to write the colours into.  Nothing
+    is launched for an empty output."""
+    image_u8 = _chk(image_u8, "image_u8", torch.uint8)
+    if image_u8.dim() != 3:
+        raise ValueError(f"image_u8 must be (H, W, 4) or (4, H, W), got {tuple(image_u8.shape)}")
+    if layout is None:
+        first, last = image_u8.shape[0] == 4, image_u8.shape[2] == 4
+        if first and last:
+            raise ValueError(f"image_u8 {tuple(image_u8.shape)} reads as (H, W, 4) and as (4, H, W): pass layout='hwc' or layout='chw'")
+        if not (first or last):
+            raise ValueError(f"image_u8 must have four bands, (H, W, 4) or (4, H, W), got {tuple(image_u8.shape)}")
+        layout = "chw" if first else "hwc"
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if image_u8.shape[0 if layout == "chw" else 2] != 4:
+        raise ValueError(f"image_u8 {tuple(image_u8.shape)} does not have four bands in layout {layout!r}")
+    h, w = (image_u8.shape[1], image_u8.shape[2]) if layout == "chw" else (image_u8.shape[0], image_u8.shape[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"image_u8 must be at least 1 x 1, got {h} x {w}")
+    strides = (w, 1, h * w) if layout == "chw" else (4 * w, 4, 1)
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h < 0 or out_w < 0:
+        raise ValueError(f"out_h and out_w must be >= 0, got {out_h} and {out_w}")
+    n, dev = out_h * out_w, image_u8.device
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev) if out is None else _chk(out, "out")
+    if tuple(out.shape) != (n, 3):
+        raise ValueError(f"out must be ({n}, 3), got {tuple(out.shape)}")
+    mask = torch.empty(n, dtype=torch.bool, device=dev)
+    rgba = torch.empty(out_h, out_w, 4, dtype=torch.uint8, device=dev) if want_rgba else None
+    coef_w, ksize_w = _lanczos_device(w, out_w, dev) if n and out_w != w else (None, 0)
+    coef_h, ksize_h = _lanczos_device(h, out_h, dev) if n and out_h != h else (None, 0)
+    nbytes = blender_colors_scratch(h, w, out_h, out_w)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    _lib.call("sr_blender_colors", _p(image_u8), h, w, strides[0], strides[1], strides[2], out_h, out_w, _p(coef_w), ksize_w, _p(coef_h),
+              ksize_h, _p(scratch), nbytes, _p(out), _p(mask), _p(rgba), 0, _stream())
+    return (out, mask, rgba) if want_rgba else (out, mask)
+
+
+def pinhole_rays(h, w, fx, fy, cx, cy, c2w, near, far, out=None):
+    """sr_pinhole_rays: the (h * w, 8) fp32 rows [o, d, near, far] of a pinhole camera, get_ray_directions + get_rays of the reference
+    (datasets/blender.py:12-59): pixel (r, c) looks along ((c - cx) / fx, -(r - cy) / fy, -1) rotated by c2w[:, :3] and normalised, from
+    c2w[:, 3].  ``c2w``: 12 host values, (3, 4) row-major; it and the scalars are rounded to fp32 first, as the reference's tensors hold
+    them.  ``out`` = an (h * w, 8) fp32 device tensor with contiguous rows to write into; without it the rows go to the current device."""
+    import numpy as np
+
+    h, w = int(h), int(w)
+    if h < 0 or w < 0:
+        raise ValueError(f"h and w must be >= 0, got {h} and {w}")
+    m = np.ascontiguousarray(np.asarray(c2w.cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float32))
+    if m.shape != (3, 4):
+        raise ValueError(f"c2w must be (3, 4), got {m.shape}")
+    n = h * w
+    out = torch.empty(n, 8, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device())) if out is None else _chk(out, "out")
+    if tuple(out.shape) != (n, 8):
+        raise ValueError(f"out must be ({n}, 8), got {tuple(out.shape)}")
+    _lib.call("sr_pinhole_rays", h, w, float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+              m.ctypes.data_as(C.POINTER(C.c_float)), float(np.float32(near)), float(np.float32(far)), _p(out), _stream())
     return out
