@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(kLanes* kRows) convert_kernel(Source src, int 
   finish(out, (int64_t)r * n_cols + c, load_pixel<PACKED>(src, r, c));
 }
 
-inline dim3 grid_for(int n_rows, int n_cols) { return dim3((unsigned)((n_cols + kLanes - 1) / kLanes), (unsigned)((n_rows + kRows - 1) / kRows)); }
+inline dim3 grid_for(int n_rows, int n_cols) { return dim3(blocks_for(n_cols, kLanes), blocks_for(n_rows, kRows)); }
 
 struct Pinhole {
   float fx, fy, cx, cy, m[12], near, far;
@@ -190,8 +190,9 @@ extern "C" int sr_blender_colors_scratch(int src_h, int src_w, int out_h, int ou
              "sr_blender_colors_scratch: the source sides must lie in 1..%d (got %d x %d)", kMaxSide, src_h, src_w);
   SR_REQUIRE(out_h >= 0 && out_w >= 0 && out_h <= kMaxSide && out_w <= kMaxSide,
              "sr_blender_colors_scratch: the output sides must lie in 0..%d (got %d x %d)", kMaxSide, out_h, out_w);
-  const bool both = out_h != src_h && out_w != src_w && out_h > 0 && out_w > 0;
-  *bytes = both ? 4 * (int64_t)src_h * out_w : 0;
+  ScratchCarver c(nullptr);
+  if (out_h != src_h && out_w != src_w && out_h > 0 && out_w > 0) c.take<uint32_t>((int64_t)src_h * out_w, 4);  // both passes run
+  *bytes = c.bytes();
   return 0;
 }
 
@@ -239,7 +240,7 @@ extern "C" int sr_blender_colors(const uint8_t* src, int src_h, int src_w, int64
       hipLaunchKernelGGL(convert_kernel<false>, grid_for(out_h, out_w), block, 0, s, from, out_h, out_w, out);
     return check_launch("blender convert_kernel");
   }
-  uint32_t* mid = static_cast<uint32_t*>(scratch);
+  uint32_t* mid = ScratchCarver(scratch).take<uint32_t>((int64_t)src_h * out_w, 4);  // the one piece; unused unless both passes run
   if (horiz) {  // (src_h, out_w) from the source
     const Axis a = axis(src_w, out_w, coef_w, ksize_w);
     const int last = !vert;

@@ -5,6 +5,7 @@
 // the cell index is IEEE fp64 division + round-half-even and must equal numpy's.
 #include <math.h>
 
+#include "block_device.h"
 #include "common.h"
 
 namespace sr {
@@ -17,15 +18,6 @@ constexpr unsigned long long kInf = ~0ull;  // pads a segment to a power of two:
 
 enum { kRuleNearest = 0, kRuleFloor = 1 };
 enum { kMin = 0, kMax = 1, kAvg = 2, kMed = 3 };
-
-// fp64 <-> uint64 keys whose unsigned order is the numeric order (-0 below +0)
-__device__ __forceinline__ unsigned long long order_key(double x) {
-  const unsigned long long b = __double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double from_key(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
 
 // ---- stage 1: key[i] = output cell of point i (-1 when dropped), count[cell] += 1 ----------------------------------------------------
 // nearest: col = rint((e - x0) / d), row = rint((n - y0) / d), output row map_h - 1 - row (the reference's flipud).  -0 counts as 0.
@@ -267,21 +259,23 @@ __global__ void __launch_bounds__(256) reduce_kernel(const int* __restrict__ cou
 
 // scratch layout (bytes): vals 8 n | key 4 n | offs 4 cells | cursor 4 cells | bsum 4 nb | n_long 4 | longs 4 (n / 65), each rounded to 8
 struct Layout {
-  int64_t vals, key, offs, cursor, bsum, n_long, longs, bytes;
+  unsigned long long* vals;
+  int *key, *offs, *cursor, *bsum, *n_long, *longs;
+  int64_t bytes;
   int nb;
 };
-static int64_t up8(int64_t b) { return (b + 7) / 8 * 8; }
-static Layout layout(int64_t n, int64_t cells) {
+static Layout layout(void* base, int64_t n, int64_t cells) {
+  ScratchCarver c(base);
   Layout l;
   l.nb = (int)((cells + kScanBlock - 1) / kScanBlock);
-  l.vals = 0;
-  l.key = l.vals + 8 * n;
-  l.offs = l.key + up8(4 * n);
-  l.cursor = l.offs + up8(4 * cells);
-  l.bsum = l.cursor + up8(4 * cells);
-  l.n_long = l.bsum + up8(4 * (int64_t)l.nb);
-  l.longs = l.n_long + 8;
-  l.bytes = l.longs + up8(4 * (n / (kWaveCap + 1)));
+  l.vals = c.take<unsigned long long>(n, 8);
+  l.key = c.take<int>(n, 8);
+  l.offs = c.take<int>(cells, 8);
+  l.cursor = c.take<int>(cells, 8);
+  l.bsum = c.take<int>(l.nb, 8);
+  l.n_long = c.take<int>(1, 8);
+  l.longs = c.take<int>(n / (kWaveCap + 1), 8);
+  l.bytes = c.bytes();
   return l;
 }
 
@@ -303,7 +297,7 @@ static int check_sizes(const char* who, int64_t n, int map_w, int map_h) {
 extern "C" int sr_cloud_grid_scratch(int64_t n, int map_w, int map_h, int64_t* bytes) {
   SR_REQUIRE(bytes, "sr_cloud_grid_scratch: null pointer");
   if (check_sizes("sr_cloud_grid_scratch", n, map_w, map_h)) return 1;
-  *bytes = layout(n, (int64_t)map_w * map_h).bytes;
+  *bytes = layout(nullptr, n, (int64_t)map_w * map_h).bytes;
   return 0;
 }
 
@@ -319,55 +313,46 @@ extern "C" int sr_cloud_grid(const double* east, const double* north, const doub
   SR_REQUIRE(isfinite(x0) && isfinite(y0), "sr_cloud_grid: non-finite grid origin");
   SR_REQUIRE(stages >= 0 && stages <= 5, "sr_cloud_grid: stages must be in 0..5 (got %d)", stages);
   const int cells = map_w * map_h;
-  const Layout l = layout(n, cells);
-  SR_REQUIRE(scratch && scratch_bytes >= l.bytes, "sr_cloud_grid: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes,
-             (long long)l.bytes);
+  const Layout l = layout(scratch, n, cells);
+  if (require_scratch("sr_cloud_grid", scratch ? scratch_bytes : 0, l.bytes)) return 1;
   SR_REQUIRE(((uintptr_t)scratch & 7) == 0, "sr_cloud_grid: scratch must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  char* base = static_cast<char*>(scratch);
-  unsigned long long* vals = reinterpret_cast<unsigned long long*>(base + l.vals);
-  int* key = reinterpret_cast<int*>(base + l.key);
-  int* offs = reinterpret_cast<int*>(base + l.offs);
-  int* cursor = reinterpret_cast<int*>(base + l.cursor);
-  int* bsum = reinterpret_cast<int*>(base + l.bsum);
-  int* n_long = reinterpret_cast<int*>(base + l.n_long);
-  int* longs = reinterpret_cast<int*>(base + l.longs);
   const int last = stages == 0 ? 5 : stages;
   const int ni = (int)n;
-  const unsigned pgrid = (unsigned)((n + 255) / 256), cgrid = (unsigned)((cells + 255) / 256);
+  const unsigned pgrid = blocks_for(n), cgrid = blocks_for(cells);
 
   if (hipMemsetAsync(count, 0, (size_t)cells * sizeof(int), s) != hipSuccess) {
     set_error("sr_cloud_grid: hipMemsetAsync of the counts failed");
     return 2;
   }
   if (n > 0) {
-    hipLaunchKernelGGL(key_count_kernel, dim3(pgrid), dim3(256), 0, s, east, north, alt, ni, x0, y0, definition, map_w, map_h, rule, key,
+    hipLaunchKernelGGL(key_count_kernel, dim3(pgrid), dim3(256), 0, s, east, north, alt, ni, x0, y0, definition, map_w, map_h, rule, l.key,
                        count);
     if (check_launch("cloud_grid key_count_kernel")) return 2;
     if (last >= 2) {
-      hipLaunchKernelGGL(scan_sums_kernel, dim3(l.nb), dim3(256), 0, s, count, cells, bsum);
+      hipLaunchKernelGGL(scan_sums_kernel, dim3(l.nb), dim3(256), 0, s, count, cells, l.bsum);
       if (check_launch("cloud_grid scan_sums_kernel")) return 2;
-      hipLaunchKernelGGL(scan_carry_kernel, dim3(1), dim3(256), 0, s, bsum, l.nb, n_long);
+      hipLaunchKernelGGL(scan_carry_kernel, dim3(1), dim3(256), 0, s, l.bsum, l.nb, l.n_long);
       if (check_launch("cloud_grid scan_carry_kernel")) return 2;
-      hipLaunchKernelGGL(scan_add_kernel, dim3(l.nb), dim3(256), 0, s, count, cells, bsum, offs, cursor);
+      hipLaunchKernelGGL(scan_add_kernel, dim3(l.nb), dim3(256), 0, s, count, cells, l.bsum, l.offs, l.cursor);
       if (check_launch("cloud_grid scan_add_kernel")) return 2;
     }
     if (last >= 3) {
-      hipLaunchKernelGGL(scatter_kernel, dim3(pgrid), dim3(256), 0, s, alt, ni, key, cursor, vals);
+      hipLaunchKernelGGL(scatter_kernel, dim3(pgrid), dim3(256), 0, s, alt, ni, l.key, l.cursor, l.vals);
       if (check_launch("cloud_grid scatter_kernel")) return 2;
     }
     if (last >= 4) {
-      hipLaunchKernelGGL(sort_wave_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, s, count, offs, cells, vals, n_long, longs);
+      hipLaunchKernelGGL(sort_wave_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, s, count, l.offs, cells, l.vals, l.n_long, l.longs);
       if (check_launch("cloud_grid sort_wave_kernel")) return 2;
       const int64_t max_long = n / (kWaveCap + 1) < cells ? n / (kWaveCap + 1) : cells;  // segments longer than kWaveCap
       if (max_long > 0) {
-        hipLaunchKernelGGL(sort_long_kernel, dim3((unsigned)max_long), dim3(256), 0, s, count, offs, vals, n_long, longs);
+        hipLaunchKernelGGL(sort_long_kernel, dim3((unsigned)max_long), dim3(256), 0, s, count, l.offs, l.vals, l.n_long, l.longs);
         if (check_launch("cloud_grid sort_long_kernel")) return 2;
       }
     }
   }
   if (last >= 5) {
-    hipLaunchKernelGGL(reduce_kernel, dim3(cgrid), dim3(256), 0, s, count, offs, cells, vals, mode, out);
+    hipLaunchKernelGGL(reduce_kernel, dim3(cgrid), dim3(256), 0, s, count, l.offs, cells, l.vals, mode, out);
     if (check_launch("cloud_grid reduce_kernel")) return 2;
   }
   return 0;

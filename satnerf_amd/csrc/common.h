@@ -28,6 +28,35 @@ bool ensure_dynamic_lds(const void* kernel, size_t bytes);
     }                          \
   } while (0)
 
+// ---- host helpers of the entry points ------------------------------------------------------------------------------------------
+inline unsigned blocks_for(int64_t n, int threads = 256) { return (unsigned)((n + threads - 1) / threads); }  // workgroups for n items
+inline int64_t align_up(int64_t bytes, int64_t a) { return (bytes + a - 1) / a * a; }
+// partial slots (= workgroups) of a reduction launch: clamp(ceil(work / per), 1, max); grid-strided beyond max
+inline long partial_slots(int64_t work, int64_t per, long max) {
+  const int64_t p = (work + per - 1) / per;
+  return p < 1 ? 1 : (p < max ? (long)p : max);
+}
+
+// Carves a caller's scratch into pieces in the order they are taken, each piece's byte count rounded up to `align` (so with an
+// aligned base every piece is aligned).  Built on nullptr it hands out nulls and only counts: the *_scratch entries' sizes.
+struct ScratchCarver {
+  explicit ScratchCarver(void* base) : base_(static_cast<char*>(base)) {}
+  template <typename T>
+  T* take(int64_t count, int64_t align) {
+    char* p = base_ ? base_ + off_ : nullptr;
+    off_ += align_up(count * (int64_t)sizeof(T), align);
+    return reinterpret_cast<T*>(p);
+  }
+  int64_t bytes() const { return off_; }
+  char* base_;
+  int64_t off_ = 0;
+};
+
+inline int require_scratch(const char* fn, int64_t have, int64_t need) {
+  SR_REQUIRE(have >= need, "%s: scratch holds %lld bytes, %lld needed", fn, (long long)have, (long long)need);
+  return 0;
+}
+
 // tiles a training workspace holds for n_points points (sr_workspace_tiles): whole workgroups of 8 waves = 8 tiles
 constexpr long ws_tiles(long n_points) { return ((n_points + 31) / 32 + 7) / 8 * 8; }
 // bytes of the exponent-maxima table behind the dpre workspace (SR_FMT8; mlp_layout.h): 16 per 4 tiles, rounded up to whole 1-KiB units

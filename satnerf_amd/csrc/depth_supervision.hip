@@ -11,8 +11,8 @@
 // no float atomics, no host synchronisation.
 #include <limits.h>
 #include <math.h>
-#include <string.h>
 
+#include "block_device.h"
 #include "common.h"
 #include "geo_device.h"
 #include "rpc_device.h"
@@ -23,24 +23,15 @@ namespace dsup {
 constexpr int kThreads = 256;
 constexpr int kMaxPartials = 2048;  // workgroups (= partial slots) of the per-point sum: grid-strided beyond that
 
-inline long point_partials(int64_t n_pts) {
-  const long p = (long)((n_pts + kThreads - 1) / kThreads);
-  return p < 1 ? 1 : (p < kMaxPartials ? p : kMaxPartials);
-}
+inline long point_partials(int64_t n_pts) { return partial_slots(n_pts, kThreads, kMaxPartials); }
 
-inline int64_t winner_bytes(int64_t n_pts, int n_cams) { return (n_pts * n_cams * (int64_t)sizeof(int) + 255) / 256 * 256; }
-
-// Fixed-order workgroup sum: shuffles within each wave, then thread 0 adds the four wave sums in order.  Thread 0 returns the total.
-__device__ __forceinline__ double block_sum(double a) {
-  __shared__ double red[kThreads / 64];
-  for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = red[0];
-    for (int k = 1; k < kThreads / 64; ++k) a += red[k];
-  }
-  return a;
+// scratch: winner (n_pts, n_cams) ints, rounded to 256 bytes | part P doubles (base == nullptr: sizes only)
+struct Scratch { int* winner; double* part; int64_t bytes; };
+inline Scratch scratch_layout(void* base, int64_t n_pts, int n_cams) {
+  ScratchCarver c(base);
+  int* winner = c.take<int>(n_pts * n_cams, 256);
+  double* part = c.take<double>(point_partials(n_pts), 8);
+  return {winner, part, c.bytes()};
 }
 
 // get_rays + normalize_rays + sun (datasets/satellite_depth.py:64-75) at n keypoints colrow = (col, row) fp64 pairs
@@ -90,7 +81,7 @@ __global__ void __launch_bounds__(kThreads) point_sum_kernel(const int* __restri
                                                              int n_cams, float* __restrict__ e, double* __restrict__ part) {
 #pragma clang fp contract(off)
   const int64_t P = gridDim.x;
-  double s = 0.0;
+  double s[1] = {0.0};
   for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < n_pts; p += P * kThreads) {
     double acc = 0.0;
     const int* wrow = winner + p * n_cams;
@@ -100,19 +91,19 @@ __global__ void __launch_bounds__(kThreads) point_sum_kernel(const int* __restri
     }
     const float ef = (float)acc;
     e[p] = ef;
-    s += (double)ef;
+    s[0] += (double)ef;
   }
-  s = block_sum(s);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
+  block_sum(s);
+  if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
-// e_mean = (sum of the P partials, thread t taking t, t + 256, ..., then block_sum's fixed tree) / n_pts, rounded to fp32.  One workgroup.
+// e_mean = (sum of the P partials: strided_sum, then block_sum's fixed tree) / n_pts, rounded to fp32.  One workgroup.
 __global__ void __launch_bounds__(kThreads) finalize_kernel(const double* __restrict__ part, int P, int64_t n_pts, float* __restrict__ e_mean) {
 #pragma clang fp contract(off)
-  double s = 0.0;
-  for (int k = threadIdx.x; k < P; k += kThreads) s += part[k];
-  s = block_sum(s);
-  if (threadIdx.x == 0) e_mean[0] = (float)(s / (double)n_pts);
+  double s[1];
+  strided_sum(part, P, s);
+  block_sum(s);
+  if (threadIdx.x == 0) e_mean[0] = (float)(s[0] / (double)n_pts);
 }
 
 // weights = np.exp(-(e / e_mean) ** 2) on fp32 arrays (satellite_depth.py:127)
@@ -151,16 +142,6 @@ __global__ void __launch_bounds__(kThreads) depths_kernel(const float* __restric
 using namespace sr;
 using namespace sr::dsup;
 
-static int load_rpc(const char* fn, const double* rpc, RpcModel& m) {
-  SR_REQUIRE(rpc, "%s: null rpc", fn);
-  static_assert(sizeof(RpcModel) == 90 * sizeof(double), "RpcModel layout = the 90 host doubles");
-  memcpy(&m, rpc, sizeof(m));
-  SR_REQUIRE(m.row_scale != 0 && m.col_scale != 0 && m.lat_scale != 0 && m.lon_scale != 0 && m.alt_scale != 0, "%s: zero RPC scale", fn);
-  return 0;
-}
-
-static unsigned blocks(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 extern "C" int sr_rpc_rays_at(const double* rpc, const double* colrow, int64_t n, double min_alt, double max_alt, const double* center,
                               double range, double sun_elevation_deg, double sun_azimuth_deg, float* rays11, void* stream) {
   SR_REQUIRE(center && (n == 0 || (colrow && rays11)), "sr_rpc_rays_at: null pointer");
@@ -169,10 +150,10 @@ extern "C" int sr_rpc_rays_at(const double* rpc, const double* colrow, int64_t n
   RpcModel m;
   if (load_rpc("sr_rpc_rays_at", rpc, m)) return 1;
   if (n == 0) return 0;
-  const double el = sun_elevation_deg * (3.141592653589793 / 180.0), az = sun_azimuth_deg * (3.141592653589793 / 180.0);
-  hipLaunchKernelGGL(rays_at_kernel, dim3(blocks(n)), dim3(kThreads), 0, (hipStream_t)stream, m, colrow, (long)n, min_alt, max_alt,
-                     (float)center[0], (float)center[1], (float)center[2], (float)range, (float)(sin(az) * cos(el)), (float)(cos(az) * cos(el)),
-                     (float)sin(el), rays11);
+  float sun[3];
+  sun_direction(sun_elevation_deg, sun_azimuth_deg, sun);
+  hipLaunchKernelGGL(rays_at_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream, m, colrow, (long)n, min_alt, max_alt,
+                     (float)center[0], (float)center[1], (float)center[2], (float)range, sun[0], sun[1], sun[2], rays11);
   return check_launch("rays_at_kernel");
 }
 
@@ -184,7 +165,7 @@ extern "C" int sr_reprojection_errors(const double* rpc, const double* colrow, c
   RpcModel m;
   if (load_rpc("sr_reprojection_errors", rpc, m)) return 1;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(reproj_kernel, dim3(blocks(n)), dim3(kThreads), 0, (hipStream_t)stream, m, colrow, pts3d_idx, (long)n, pts3d, n_pts, err);
+  hipLaunchKernelGGL(reproj_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream, m, colrow, pts3d_idx, (long)n, pts3d, n_pts, err);
   return check_launch("reproj_kernel");
 }
 
@@ -192,7 +173,7 @@ extern "C" int sr_keypoint_weights_scratch(int64_t n_pts, int n_cams, int64_t* b
   SR_REQUIRE(bytes, "sr_keypoint_weights_scratch: null pointer");
   SR_REQUIRE(n_pts >= 1 && n_cams >= 1 && n_pts <= ((int64_t)1 << 36) / n_cams,
              "sr_keypoint_weights_scratch: need n_pts >= 1, n_cams >= 1 and n_pts * n_cams <= 2^36 (got %lld x %d)", (long long)n_pts, n_cams);
-  *bytes = winner_bytes(n_pts, n_cams) + point_partials(n_pts) * (int64_t)sizeof(double);
+  *bytes = scratch_layout(nullptr, n_pts, n_cams).bytes;
   return 0;
 }
 
@@ -202,21 +183,20 @@ extern "C" int sr_keypoint_weights(const int64_t* pts3d_idx, const int64_t* cam,
   if (sr_keypoint_weights_scratch(n_pts, n_cams, &need)) return 1;
   SR_REQUIRE(scratch && e && w && e_mean && (n == 0 || (pts3d_idx && cam && err)), "sr_keypoint_weights: null pointer");
   SR_REQUIRE(n >= 0 && n < INT_MAX, "sr_keypoint_weights: n must be in 0..%d (got %lld)", INT_MAX - 1, (long long)n);
-  SR_REQUIRE(scratch_bytes >= need, "sr_keypoint_weights: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
+  if (require_scratch("sr_keypoint_weights", scratch_bytes, need)) return 1;
   hipStream_t s = (hipStream_t)stream;
-  int* winner = static_cast<int*>(scratch);
-  double* part = reinterpret_cast<double*>(static_cast<char*>(scratch) + winner_bytes(n_pts, n_cams));
+  const Scratch sc = scratch_layout(scratch, n_pts, n_cams);
   const long P = point_partials(n_pts);
-  SR_REQUIRE(hipMemsetAsync(winner, 0, (size_t)n_pts * n_cams * sizeof(int), s) == hipSuccess, "sr_keypoint_weights: hipMemsetAsync failed");
+  SR_REQUIRE(hipMemsetAsync(sc.winner, 0, (size_t)n_pts * n_cams * sizeof(int), s) == hipSuccess, "sr_keypoint_weights: hipMemsetAsync failed");
   if (n > 0) {
-    hipLaunchKernelGGL(scatter_kernel, dim3(blocks(n)), dim3(kThreads), 0, s, pts3d_idx, cam, (long)n, n_pts, n_cams, winner);
+    hipLaunchKernelGGL(scatter_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, pts3d_idx, cam, (long)n, n_pts, n_cams, sc.winner);
     if (check_launch("scatter_kernel")) return 2;
   }
-  hipLaunchKernelGGL(point_sum_kernel, dim3((unsigned)P), dim3(kThreads), 0, s, (const int*)winner, err, n_pts, n_cams, e, part);
+  hipLaunchKernelGGL(point_sum_kernel, dim3((unsigned)P), dim3(kThreads), 0, s, (const int*)sc.winner, err, n_pts, n_cams, e, sc.part);
   if (check_launch("point_sum_kernel")) return 2;
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)part, (int)P, n_pts, e_mean);
+  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)sc.part, (int)P, n_pts, e_mean);
   if (check_launch("finalize_kernel")) return 2;
-  hipLaunchKernelGGL(weights_kernel, dim3(blocks(n_pts)), dim3(kThreads), 0, s, (const float*)e, n_pts, (const float*)e_mean, w);
+  hipLaunchKernelGGL(weights_kernel, dim3(blocks_for(n_pts)), dim3(kThreads), 0, s, (const float*)e, n_pts, (const float*)e_mean, w);
   return check_launch("weights_kernel");
 }
 
@@ -227,7 +207,7 @@ extern "C" int sr_tie_point_depths(const float* rays11, const double* pts3d, con
              (long long)n_pts);
   SR_REQUIRE(range > 0, "sr_tie_point_depths: scene range must be positive");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(depths_kernel, dim3(blocks(n)), dim3(kThreads), 0, (hipStream_t)stream, rays11, pts3d, pts3d_idx, (long)n, n_pts,
+  hipLaunchKernelGGL(depths_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream, rays11, pts3d, pts3d_idx, (long)n, n_pts,
                      (float)center[0], (float)center[1], (float)center[2], (float)range, w, depths);
   return check_launch("depths_kernel");
 }

@@ -3,6 +3,7 @@
 // bitwise the same for any arrival (and point) order, for every sigma.
 #include <math.h>
 
+#include "block_device.h"
 #include "common.h"
 #include "geo_device.h"
 
@@ -107,15 +108,7 @@ __device__ __forceinline__ bool usable(double e, double nn, double al) {
   return isfinite(e) && isfinite(nn) && isfinite(al) && fabs(al) <= kMaxAbsAlt;
 }
 
-// fp64 <-> uint64 keys whose unsigned order is the numeric order, so min / max are exact integer atomics (order-independent).
-__device__ __forceinline__ unsigned long long order_key(double x) {
-  const unsigned long long b = __double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double from_key(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
+// bounds as order_key keys (block_device.h): min / max are exact integer atomics (order-independent)
 __global__ void bounds_init_kernel(unsigned long long* keys) {
   keys[0] = ~0ull, keys[1] = 0, keys[2] = ~0ull, keys[3] = 0;  // min, max, min, max
 }
@@ -131,12 +124,7 @@ __global__ void __launch_bounds__(256) bounds_kernel(const double* __restrict__ 
     k[0] = ke < k[0] ? ke : k[0], k[1] = ke > k[1] ? ke : k[1];
     k[2] = kn < k[2] ? kn : k[2], k[3] = kn > k[3] ? kn : k[3];
   }
-  for (int off = 32; off >= 1; off >>= 1) {
-    for (int v = 0; v < 4; ++v) {
-      const unsigned long long o = __shfl_xor(k[v], off);
-      k[v] = (v & 1) ? (o > k[v] ? o : k[v]) : (o < k[v] ? o : k[v]);
-    }
-  }
+  wave_minmax(k);
   if ((threadIdx.x & 63) == 0) {
     atomicMin(keys + 0, k[0]), atomicMax(keys + 1, k[1]);
     atomicMin(keys + 2, k[2]), atomicMax(keys + 3, k[3]);
@@ -209,8 +197,6 @@ __global__ void __launch_bounds__(256) dsm_finalize_kernel(const unsigned long l
 
 using namespace sr;
 
-static unsigned grid_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 extern "C" int sr_utm_zone(double lat, double lon, int* zone, int* letter) {
   SR_REQUIRE(zone && letter, "sr_utm_zone: null pointer");
   SR_REQUIRE(isfinite(lon) && lat >= -80 && lat <= 84, "sr_utm_zone: need -80 <= lat <= 84 and a finite lon (got %g, %g)", lat, lon);
@@ -223,7 +209,7 @@ extern "C" int sr_utm_from_latlon(const double* lat, const double* lon, int64_t 
   SR_REQUIRE(zone >= 1 && zone <= 60, "sr_utm_from_latlon: zone must be in 1..60 (got %d)", zone);
   if (n <= 0) return 0;
   SR_REQUIRE(lat && lon && east && north, "sr_utm_from_latlon: null pointer");
-  hipLaunchKernelGGL(utm_kernel, dim3(grid_of(n)), dim3(256), 0, (hipStream_t)stream, lat, lon, (long)n, zone, east, north);
+  hipLaunchKernelGGL(utm_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, lat, lon, (long)n, zone, east, north);
   return check_launch("utm_kernel");
 }
 
@@ -236,7 +222,7 @@ extern "C" int sr_depth_to_utm(const float* rays, int ray_stride, const float* d
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(depth_zone_kernel, dim3(1), dim3(1), 0, s, rays, depth, center[0], center[1], center[2], range, zone, zone_out);
   if (check_launch("depth_zone_kernel")) return 2;
-  hipLaunchKernelGGL(depth_utm_kernel, dim3(grid_of(n_rays)), dim3(256), 0, s, rays, ray_stride, depth, (long)n_rays, center[0], center[1],
+  hipLaunchKernelGGL(depth_utm_kernel, dim3(blocks_for(n_rays)), dim3(256), 0, s, rays, ray_stride, depth, (long)n_rays, center[0], center[1],
                      center[2], range, zone_out, east, north, alt);
   return check_launch("depth_utm_kernel");
 }
@@ -249,7 +235,7 @@ extern "C" int sr_dsm_bounds(const double* east, const double* north, const doub
   hipLaunchKernelGGL(bounds_init_kernel, dim3(1), dim3(1), 0, s, keys);
   if (check_launch("bounds_init_kernel")) return 2;
   if (n > 0) {
-    const unsigned blocks = (unsigned)(grid_of(n) < 1024 ? grid_of(n) : 1024);
+    const unsigned blocks = blocks_for(n) < 1024 ? blocks_for(n) : 1024;
     hipLaunchKernelGGL(bounds_kernel, dim3(blocks), dim3(256), 0, s, east, north, alt, (long)n, keys);
     if (check_launch("bounds_kernel")) return 2;
   }
@@ -274,11 +260,11 @@ extern "C" int sr_dsm_rasterize(const double* east, const double* north, const d
     return 2;
   }
   if (n > 0) {
-    hipLaunchKernelGGL(splat_kernel, dim3(grid_of(n)), dim3(256), 0, s, east, north, alt, (long)n, xoff, yoff, resolution, xsize, ysize,
+    hipLaunchKernelGGL(splat_kernel, dim3(blocks_for(n)), dim3(256), 0, s, east, north, alt, (long)n, xoff, yoff, resolution, xsize, ysize,
                        radius, sigma, reinterpret_cast<unsigned long long*>(acc));
     if (check_launch("splat_kernel")) return 2;
   }
-  hipLaunchKernelGGL(dsm_finalize_kernel, dim3(grid_of(cells)), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(acc),
+  hipLaunchKernelGGL(dsm_finalize_kernel, dim3(blocks_for(cells)), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(acc),
                      (long)cells, dsm, weight);
   return check_launch("dsm_finalize_kernel");
 }

@@ -227,32 +227,34 @@ __global__ void __launch_bounds__(256) apply_kernel(const double* __restrict__ v
 struct Plan {
   int levels;
   int hu[16], wu[16], hv[16], wv[16];
-  long img_off[16][2];  // doubles from the scratch base of level k's u / v (k >= 1)
-  long part_off, stats_off, cur_off, total;  // doubles; total rounded to whole doubles
-  int S, parts0;
+  double* img[16][2];  // level k's u / v (k >= 1)
+  double *part, *stats;
+  int* cur;       // 2 ints
+  int64_t bytes;  // whole doubles
+  int S;
 };
 
 inline int tiles_of(int h, int w) { return ((h + kTH - 1) / kTH) * ((w + kTW - 1) / kTW); }
-inline int partials_of(int h, int w) { return tiles_of(h, w) < kMaxPartials ? tiles_of(h, w) : kMaxPartials; }
+inline int partials_of(int h, int w) { return (int)partial_slots(tiles_of(h, w), 1, kMaxPartials); }
 
-inline Plan make_plan(int hu, int wu, int hv, int wv, int r) {
+// base == nullptr: sizes only
+inline Plan make_plan(void* base, int hu, int wu, int hv, int wv, int r) {
   Plan p{};
+  ScratchCarver c(base);
   p.hu[0] = hu, p.wu[0] = wu, p.hv[0] = hv, p.wv[0] = wv;
   p.levels = 1;
-  long off = 0;
   while ((p.hu[p.levels - 1] < p.wu[p.levels - 1] ? p.hu[p.levels - 1] : p.wu[p.levels - 1]) > 100) {
     const int k = p.levels++;
     p.hu[k] = (p.hu[k - 1] + 1) / 2, p.wu[k] = (p.wu[k - 1] + 1) / 2;
     p.hv[k] = (p.hv[k - 1] + 1) / 2, p.wv[k] = (p.wv[k - 1] + 1) / 2;
-    p.img_off[k][0] = off, off += (long)p.hu[k] * p.wu[k];
-    p.img_off[k][1] = off, off += (long)p.hv[k] * p.wv[k];
+    p.img[k][0] = c.take<double>((int64_t)p.hu[k] * p.wu[k], 8);
+    p.img[k][1] = c.take<double>((int64_t)p.hv[k] * p.wv[k], 8);
   }
   p.S = (2 * r + 1) * (2 * r + 1);
-  p.parts0 = partials_of(hu, wu);  // level 0 has the most tiles
-  p.part_off = off, off += 3L * p.S * p.parts0;
-  p.stats_off = off, off += (long)kStat * p.S;
-  p.cur_off = off, off += 1;  // 2 ints
-  p.total = off;
+  p.part = c.take<double>(3L * p.S * partials_of(hu, wu), 8);  // level 0 has the most tiles
+  p.stats = c.take<double>((int64_t)kStat * p.S, 8);
+  p.cur = c.take<int>(2, 8);
+  p.bytes = c.bytes();
   return p;
 }
 
@@ -261,8 +263,6 @@ inline Plan make_plan(int hu, int wu, int hv, int wv, int r) {
 
 using namespace sr;
 using namespace sr::reg;
-
-static unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
 static int check_shape(const char* fn, int hu, int wu, int hv, int wv, int irange) {
   SR_REQUIRE(hu >= 1 && wu >= 1 && hv >= 1 && wv >= 1 && hu <= kMaxSide && wu <= kMaxSide && hv <= kMaxSide && wv <= kMaxSide,
@@ -274,8 +274,8 @@ static int check_shape(const char* fn, int hu, int wu, int hv, int wv, int irang
 extern "C" int sr_dsm_register_scratch(int hu, int wu, int hv, int wv, int irange, int64_t* bytes, int* levels) {
   SR_REQUIRE(bytes && levels, "sr_dsm_register_scratch: null pointer");
   if (check_shape("sr_dsm_register_scratch", hu, wu, hv, wv, irange)) return 1;
-  const Plan p = make_plan(hu, wu, hv, wv, irange);
-  *bytes = p.total * (int64_t)sizeof(double);
+  const Plan p = make_plan(nullptr, hu, wu, hv, wv, irange);
+  *bytes = p.bytes;
   *levels = p.levels;
   return 0;
 }
@@ -284,7 +284,7 @@ extern "C" int sr_dsm_downsample2x(const double* in, int h, int w, double* out, 
   SR_REQUIRE(in && out, "sr_dsm_downsample2x: null pointer");
   SR_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "sr_dsm_downsample2x: each side must be in 1..%d (%d x %d)", kMaxSide, h, w);
   const long cells = (long)((h + 1) / 2) * ((w + 1) / 2);
-  hipLaunchKernelGGL(downsample_kernel, dim3(blocks_of(cells), 1, 1), dim3(256), 0, (hipStream_t)stream, in, h, w, out, in, h, w, out);
+  hipLaunchKernelGGL(downsample_kernel, dim3(blocks_for(cells), 1, 1), dim3(256), 0, (hipStream_t)stream, in, h, w, out, in, h, w, out);
   return check_launch("downsample_kernel");
 }
 
@@ -293,41 +293,34 @@ extern "C" int sr_dsm_compute_shift(const double* u, int hu, int wu, const doubl
                                     void* stream) {
   SR_REQUIRE(u && v && scratch && shift && coef, "sr_dsm_compute_shift: null pointer");
   if (check_shape("sr_dsm_compute_shift", hu, wu, hv, wv, irange)) return 1;
-  const Plan p = make_plan(hu, wu, hv, wv, irange);
-  SR_REQUIRE(scratch_bytes >= p.total * (int64_t)sizeof(double), "sr_dsm_compute_shift: scratch holds %lld bytes, %lld needed",
-             (long long)scratch_bytes, (long long)(p.total * (int64_t)sizeof(double)));
+  const Plan p = make_plan(scratch, hu, wu, hv, wv, irange);
+  if (require_scratch("sr_dsm_compute_shift", scratch_bytes, p.bytes)) return 1;
   hipStream_t s = (hipStream_t)stream;
-  double* base = static_cast<double*>(scratch);
   const double* lu[16];
   const double* lv[16];
   lu[0] = u, lv[0] = v;
   for (int k = 1; k < p.levels; ++k) {
-    double* ou = base + p.img_off[k][0];
-    double* ov = base + p.img_off[k][1];
     const long cells = (long)p.hu[k] * p.wu[k] > (long)p.hv[k] * p.wv[k] ? (long)p.hu[k] * p.wu[k] : (long)p.hv[k] * p.wv[k];
-    hipLaunchKernelGGL(downsample_kernel, dim3(blocks_of(cells), 1, 2), dim3(256), 0, s, lu[k - 1], p.hu[k - 1], p.wu[k - 1], ou,
-                       lv[k - 1], p.hv[k - 1], p.wv[k - 1], ov);
+    hipLaunchKernelGGL(downsample_kernel, dim3(blocks_for(cells), 1, 2), dim3(256), 0, s, lu[k - 1], p.hu[k - 1], p.wu[k - 1], p.img[k][0],
+                       lv[k - 1], p.hv[k - 1], p.wv[k - 1], p.img[k][1]);
     if (check_launch("downsample_kernel")) return 2;
-    lu[k] = ou, lv[k] = ov;
+    lu[k] = p.img[k][0], lv[k] = p.img[k][1];
   }
-  double* part = base + p.part_off;
-  double* stats = base + p.stats_off;
-  int* cur = reinterpret_cast<int*>(base + p.cur_off);
   const unsigned nt = (unsigned)((p.S + 63) / 64 * 64 < 256 ? (p.S + 63) / 64 * 64 : 256);
   for (int k = p.levels - 1; k >= 0; --k) {
     const int tiles_x = (p.wu[k] + kTW - 1) / kTW, ntiles = tiles_of(p.hu[k], p.wu[k]), P = partials_of(p.hu[k], p.wu[k]);
-    const int* start = k == p.levels - 1 ? nullptr : cur;
+    const int* start = k == p.levels - 1 ? nullptr : p.cur;
     hipLaunchKernelGGL(stats_kernel<1>, dim3(P), dim3(nt), 0, s, lu[k], p.hu[k], p.wu[k], lv[k], p.hv[k], p.wv[k], irange, start, tiles_x,
-                       ntiles, part, (const double*)stats);
+                       ntiles, p.part, (const double*)p.stats);
     if (check_launch("stats_kernel<1>")) return 2;
-    hipLaunchKernelGGL(reduce_kernel<1>, dim3(p.S), dim3(256), 0, s, (const double*)part, P, stats);
+    hipLaunchKernelGGL(reduce_kernel<1>, dim3(p.S), dim3(256), 0, s, (const double*)p.part, P, p.stats);
     if (check_launch("reduce_kernel<1>")) return 2;
     hipLaunchKernelGGL(stats_kernel<2>, dim3(P), dim3(nt), 0, s, lu[k], p.hu[k], p.wu[k], lv[k], p.hv[k], p.wv[k], irange, start, tiles_x,
-                       ntiles, part, (const double*)stats);
+                       ntiles, p.part, (const double*)p.stats);
     if (check_launch("stats_kernel<2>")) return 2;
-    hipLaunchKernelGGL(reduce_kernel<2>, dim3(p.S), dim3(256), 0, s, (const double*)part, P, stats);
+    hipLaunchKernelGGL(reduce_kernel<2>, dim3(p.S), dim3(256), 0, s, (const double*)p.part, P, p.stats);
     if (check_launch("reduce_kernel<2>")) return 2;
-    hipLaunchKernelGGL(select_kernel, dim3(1), dim3(64), 0, s, (const double*)stats, irange, k, start, cur, scaling, ncc_levels, start_levels,
+    hipLaunchKernelGGL(select_kernel, dim3(1), dim3(64), 0, s, (const double*)p.stats, irange, k, start, p.cur, scaling, ncc_levels, start_levels,
                        shift, coef);
     if (check_launch("select_kernel")) return 2;
   }
@@ -338,6 +331,6 @@ extern "C" int sr_dsm_apply_shift(const double* v, int hv, int wv, const int* sh
   SR_REQUIRE(v && shift && coef && out, "sr_dsm_apply_shift: null pointer");
   SR_REQUIRE(hv >= 1 && wv >= 1 && hv <= kMaxSide && wv <= kMaxSide, "sr_dsm_apply_shift: each side must be in 1..%d (%d x %d)", kMaxSide,
              hv, wv);
-  hipLaunchKernelGGL(apply_kernel, dim3(blocks_of((long)hv * wv)), dim3(256), 0, (hipStream_t)stream, v, hv, wv, shift, coef, out);
+  hipLaunchKernelGGL(apply_kernel, dim3(blocks_for((long)hv * wv)), dim3(256), 0, (hipStream_t)stream, v, hv, wv, shift, coef, out);
   return check_launch("apply_kernel");
 }

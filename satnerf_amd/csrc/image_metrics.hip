@@ -7,6 +7,7 @@
 // shapes: results are bitwise repeatable, with no float atomics and no host synchronisation (capturable).
 #include <math.h>
 
+#include "block_device.h"
 #include "common.h"
 
 namespace sr {
@@ -25,32 +26,11 @@ constexpr double kG0 = 0.30780132912346997;  // x = +-1
 constexpr double kG1 = 0.38439734175306;     // x = 0
 constexpr double kC1 = 0.01 * 0.01, kC2 = 0.03 * 0.03, kEps = 1e-12;
 
-inline long sse_partials(int64_t n) {
-  const long quads = (long)((n + 3) / 4);
-  const long p = (quads + kThreads - 1) / kThreads;
-  return p < 1 ? 1 : (p < kMaxPartials ? p : kMaxPartials);
-}
+inline long sse_partials(int64_t n) { return partial_slots((n + 3) / 4, kThreads, kMaxPartials); }
 
 inline long ssim_tiles(int64_t planes, int h, int w) { return (long)planes * ((h + kTH - 1) / kTH) * ((w + kTW - 1) / kTW); }
 
-inline long ssim_partials(int64_t planes, int h, int w) {
-  const long t = ssim_tiles(planes, h, w);
-  return t < 1 ? 1 : (t < kMaxPartials ? t : kMaxPartials);
-}
-
-// Fixed-order workgroup sum of two doubles per thread: shuffles within each wave, then wave 0 adds the four wave sums in order.
-// Thread 0 of the workgroup returns the totals.
-__device__ __forceinline__ void block_sum2(double& a, double& b) {
-  __shared__ double red[2][kThreads / 64];
-  for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off), b += __shfl_xor(b, off);
-  const int wave = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) red[0][wave] = a, red[1][wave] = b;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = red[0][0], b = red[1][0];
-    for (int k = 1; k < kThreads / 64; ++k) a += red[0][k], b += red[1][k];
-  }
-}
+inline long ssim_partials(int64_t planes, int h, int w) { return partial_slots(ssim_tiles(planes, h, w), 1, kMaxPartials); }
 
 // ---- sum of squared error ----------------------------------------------------------------------------------------------------------
 // Thread t of workgroup g owns the element quads q = g * 256 + t + k * (P * 256), k = 0, 1, ..., and adds the squares of quad q's
@@ -82,8 +62,9 @@ __global__ void __launch_bounds__(kThreads) sse_kernel(const float* __restrict__
       }
     }
   }
-  block_sum2(s, c);
-  if (threadIdx.x == 0) part[blockIdx.x] = s, part[P + blockIdx.x] = c;
+  double v[2] = {s, c};
+  block_sum(v);
+  if (threadIdx.x == 0) part[blockIdx.x] = v[0], part[P + blockIdx.x] = v[1];
 }
 
 // ---- SSIM map sum ------------------------------------------------------------------------------------------------------------------
@@ -167,17 +148,17 @@ __global__ void __launch_bounds__(kThreads) ssim_kernel(const float* __restrict_
       for (int q = 0; q < 5; ++q) up[q] = mid[q], mid[q] = dn[q];
     }
   }
-  block_sum2(acc, cnt);
-  if (tid == 0) part[blockIdx.x] = acc, part[P + blockIdx.x] = cnt;
+  double v[2] = {acc, cnt};
+  block_sum(v);
+  if (tid == 0) part[blockIdx.x] = v[0], part[P + blockIdx.x] = v[1];
 }
 
-// out[0] = the P partial sums, out[1] = the P partial counts, each added in a fixed order: thread t takes t, t + 256, ..., then
-// block_sum2's fixed tree.  One workgroup.
+// out[0] = the P partial sums, out[1] = the P partial counts, each by strided_sum, then block_sum's fixed tree.  One workgroup.
 __global__ void __launch_bounds__(kThreads) finalize_kernel(const double* __restrict__ part, int P, double* __restrict__ out) {
-  double s = 0.0, c = 0.0;
-  for (int k = threadIdx.x; k < P; k += kThreads) s += part[k], c += part[P + k];
-  block_sum2(s, c);
-  if (threadIdx.x == 0) out[0] = s, out[1] = c;
+  double v[2];
+  strided_sum(part, P, v);
+  block_sum(v);
+  if (threadIdx.x == 0) out[0] = v[0], out[1] = v[1];
 }
 
 }  // namespace imgm
@@ -214,8 +195,7 @@ extern "C" int sr_image_sse(const float* pred, const float* gt, int64_t n, const
   SR_REQUIRE(!mask || (mask_div >= 1 && mask_div <= (n > 0 ? n : 1)), "sr_image_sse: mask_div must be in 1..n (got %lld)",
              (long long)mask_div);
   const long P = sse_partials(n);
-  SR_REQUIRE(scratch_bytes >= 2 * P * (int64_t)sizeof(double), "sr_image_sse: scratch holds %lld bytes, %lld needed",
-             (long long)scratch_bytes, (long long)(2 * P * sizeof(double)));
+  if (require_scratch("sr_image_sse", scratch_bytes, 2 * P * (int64_t)sizeof(double))) return 1;
   hipStream_t s = (hipStream_t)stream;
   double* part = static_cast<double*>(scratch);
   const bool vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(gt)) & 15) == 0;
@@ -233,8 +213,7 @@ extern "C" int sr_ssim_sum(const float* img1, const float* img2, int64_t planes,
   SR_REQUIRE(out && scratch && (planes == 0 || (img1 && img2)), "sr_ssim_sum: null pointer");
   if (check_ssim_shape("sr_ssim_sum", planes, h, w)) return 1;
   const long P = ssim_partials(planes, h, w);
-  SR_REQUIRE(scratch_bytes >= 2 * P * (int64_t)sizeof(double), "sr_ssim_sum: scratch holds %lld bytes, %lld needed",
-             (long long)scratch_bytes, (long long)(2 * P * sizeof(double)));
+  if (require_scratch("sr_ssim_sum", scratch_bytes, 2 * P * (int64_t)sizeof(double))) return 1;
   hipStream_t s = (hipStream_t)stream;
   double* part = static_cast<double*>(scratch);
   hipLaunchKernelGGL(ssim_kernel, dim3((unsigned)P), dim3(kThreads), 0, s, img1, img2, planes, h, w, part);

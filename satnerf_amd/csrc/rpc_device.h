@@ -2,6 +2,10 @@
 // (depth_supervision.hip), fp64 throughout with contraction off: sr_rpc_rays' output is unchanged by the move into this header.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include "common.h"
 
 namespace sr {
 
@@ -9,6 +13,21 @@ struct RpcModel {  // host-filled, passed by value (90 doubles)
   double row_num[20], row_den[20], col_num[20], col_den[20];
   double row_offset, col_offset, lat_offset, lon_offset, alt_offset, row_scale, col_scale, lat_scale, lon_scale, alt_scale;
 };
+
+// the 90 host doubles of entry point fn -> m; 1 + sr_last_error on a null pointer or a zero scale
+inline int load_rpc(const char* fn, const double* rpc, RpcModel& m) {
+  SR_REQUIRE(rpc, "%s: null rpc", fn);
+  static_assert(sizeof(RpcModel) == 90 * sizeof(double), "RpcModel layout = the 90 host doubles");
+  memcpy(&m, rpc, sizeof(m));
+  SR_REQUIRE(m.row_scale != 0 && m.col_scale != 0 && m.lat_scale != 0 && m.lon_scale != 0 && m.alt_scale != 0, "%s: zero RPC scale", fn);
+  return 0;
+}
+
+// an image's sun direction (datasets/satellite.py:199-211) from its elevation and azimuth in degrees: fp64 on the host, rounded once
+inline void sun_direction(double el_deg, double az_deg, float sun[3]) {
+  const double el = el_deg * (3.141592653589793 / 180.0), az = az_deg * (3.141592653589793 / 180.0);
+  sun[0] = (float)(sin(az) * cos(el)), sun[1] = (float)(cos(az) * cos(el)), sun[2] = (float)sin(el);
+}
 
 __device__ __forceinline__ double rpc_poly(const double* c, double x, double y, double z) {  // x = lat, y = lon, z = alt (normalised)
 #pragma clang fp contract(off)

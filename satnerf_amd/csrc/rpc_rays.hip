@@ -7,8 +7,8 @@
 // Newton iteration on the normalised projection with a finite-difference Jacobian until the squared pixel error is < 1e-18
 // (rpcm's tolerance), then the same fp32 arithmetic as the reference's in-place tensor ops for the normalisation.
 #include <math.h>
-#include <string.h>
 
+#include "block_device.h"
 #include "common.h"
 #include "rpc_device.h"
 
@@ -30,16 +30,8 @@ __global__ void __launch_bounds__(256) rpc_rays_kernel(const RpcModel m, int wid
 }
 
 // ---- ECEF bounds of one image's rays: SatelliteDataset.init_scaling_params (datasets/satellite.py:139-151) ----
-// fp32 <-> uint32 keys whose unsigned order is the numeric order (the fp64 idiom of dsm.hip): min / max become exact integer atomics,
-// so the result does not depend on the arrival order.
-__device__ __forceinline__ unsigned order_key32(float x) {
-  const unsigned b = __float_as_uint(x);
-  return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_key32(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
-constexpr unsigned kKeyPosInf = 0xff800000u;  // order_key32(+inf): the neutral element of min
-constexpr unsigned kKeyNegInf = 0x007fffffu;  // order_key32(-inf): the neutral element of max
-
+// The bounds are held as fp32 order_key keys (block_device.h): min / max become exact integer atomics, so the result does not depend
+// on the arrival order.
 __global__ void scene_bounds_init_kernel(unsigned* keys, unsigned long long* n_bad) {
   for (int v = 0; v < 6; ++v) keys[v] = (v & 1) ? kKeyNegInf : kKeyPosInf;  // min, max per axis
   *n_bad = 0;
@@ -69,7 +61,7 @@ __global__ void __launch_bounds__(256) rpc_scene_bounds_kernel(const RpcModel m,
     if (ok) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        const unsigned kn = order_key32(r8[a]), kf = order_key32(fp[a]);
+        const unsigned kn = order_key(r8[a]), kf = order_key(fp[a]);
         k[2 * a] = kn < kf ? kn : kf;
         k[2 * a + 1] = kn < kf ? kf : kn;
       }
@@ -78,11 +70,7 @@ __global__ void __launch_bounds__(256) rpc_scene_bounds_kernel(const RpcModel m,
     }
   }
   for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int v = 0; v < 6; ++v) {
-      const unsigned o = __shfl_xor(k[v], off);
-      k[v] = (v & 1) ? (o > k[v] ? o : k[v]) : (o < k[v] ? o : k[v]);
-    }
+    wave_minmax_step(k, off);
     bad += __shfl_xor(bad, off);
   }
   if ((threadIdx.x & 63) == 0) {
@@ -104,7 +92,7 @@ __global__ void __launch_bounds__(256) rpc_scene_bounds_kernel(const RpcModel m,
 // keys -> floats in place; an untouched sentinel decodes to +inf (min) / -inf (max)
 __global__ void scene_bounds_final_kernel(unsigned* keys) {
   float* out = reinterpret_cast<float*>(keys);
-  for (int v = 0; v < 6; ++v) out[v] = from_key32(keys[v]);
+  for (int v = 0; v < 6; ++v) out[v] = from_key(keys[v]);
 }
 
 }  // namespace sr
@@ -118,14 +106,12 @@ extern "C" int sr_rpc_rays(const double* rpc, int width, int height, double min_
   SR_REQUIRE(width >= 1 && height >= 1, "sr_rpc_rays: bad image size %d x %d", width, height);
   SR_REQUIRE(range > 0, "sr_rpc_rays: scene range must be positive");
   RpcModel m;
-  static_assert(sizeof(RpcModel) == 90 * sizeof(double), "RpcModel layout = the 90 host doubles");
-  memcpy(&m, rpc, sizeof(m));
-  SR_REQUIRE(m.row_scale != 0 && m.col_scale != 0 && m.lat_scale != 0 && m.lon_scale != 0 && m.alt_scale != 0, "sr_rpc_rays: zero RPC scale");
-  const double el = sun_elevation_deg * (3.141592653589793 / 180.0), az = sun_azimuth_deg * (3.141592653589793 / 180.0);
+  if (load_rpc("sr_rpc_rays", rpc, m)) return 1;
+  float sun[3];
+  sun_direction(sun_elevation_deg, sun_azimuth_deg, sun);
   const long n = (long)width * height;
-  hipLaunchKernelGGL(rpc_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, width, n, min_alt, max_alt,
-                     (float)center[0], (float)center[1], (float)center[2], (float)range, (float)(sin(az) * cos(el)), (float)(cos(az) * cos(el)),
-                     (float)sin(el), rays11, rays8);
+  hipLaunchKernelGGL(rpc_rays_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, m, width, n, min_alt, max_alt, (float)center[0],
+                     (float)center[1], (float)center[2], (float)range, sun[0], sun[1], sun[2], rays11, rays8);
   return check_launch("rpc_rays_kernel");
 }
 
@@ -134,16 +120,14 @@ extern "C" int sr_rpc_scene_bounds(const double* rpc, int width, int height, dou
   SR_REQUIRE(rpc && bounds6 && n_bad, "sr_rpc_scene_bounds: null pointer");
   SR_REQUIRE(width >= 1 && height >= 1, "sr_rpc_scene_bounds: bad image size %d x %d", width, height);
   RpcModel m;
-  memcpy(&m, rpc, sizeof(m));
-  SR_REQUIRE(m.row_scale != 0 && m.col_scale != 0 && m.lat_scale != 0 && m.lon_scale != 0 && m.alt_scale != 0,
-             "sr_rpc_scene_bounds: zero RPC scale");
+  if (load_rpc("sr_rpc_scene_bounds", rpc, m)) return 1;
   hipStream_t s = (hipStream_t)stream;
   unsigned* keys = reinterpret_cast<unsigned*>(bounds6);
   unsigned long long* bad = reinterpret_cast<unsigned long long*>(n_bad);
   const long n = (long)width * height;
   hipLaunchKernelGGL(scene_bounds_init_kernel, dim3(1), dim3(1), 0, s, keys, bad);
   if (check_launch("scene_bounds_init_kernel")) return 2;
-  hipLaunchKernelGGL(rpc_scene_bounds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m, width, n, min_alt, max_alt, keys, bad);
+  hipLaunchKernelGGL(rpc_scene_bounds_kernel, dim3(blocks_for(n)), dim3(256), 0, s, m, width, n, min_alt, max_alt, keys, bad);
   if (check_launch("rpc_scene_bounds_kernel")) return 2;
   hipLaunchKernelGGL(scene_bounds_final_kernel, dim3(1), dim3(1), 0, s, keys);
   return check_launch("scene_bounds_final_kernel");

@@ -33,8 +33,6 @@ struct GridParams {
   int gx, gy, n_valid, pad;
 };
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 // cells of the grid for k points and n neighbours: about max(2, n / 2) points per cell
 inline int64_t grid_cells(int64_t k, int n) {
   const int64_t per = n / 2 > 2 ? n / 2 : 2;
@@ -48,24 +46,18 @@ struct Scratch {
   double *sx, *sy;
 };
 
-// byte layout of the scratch (base == nullptr: sizes only)
+// byte layout of the scratch, every piece rounded to 256 bytes (base == nullptr: sizes only)
 inline int64_t scratch_layout(int64_t k, int64_t cells, void* base, Scratch* s) {
-  char* p = static_cast<char*>(base);
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* q = p ? p + off : nullptr;
-    off += align256(bytes);
-    return q;
-  };
-  GridParams* prm = (GridParams*)take(sizeof(GridParams));
-  int* start = (int*)take((cells + 2) * 4);  // the cells, the overflow bucket, the end
-  int* cell = (int*)take(k * 4);
-  int* rank = (int*)take(k * 4);
-  int* sidx = (int*)take(k * 4);
-  double* sx = (double*)take(k * 8);
-  double* sy = (double*)take(k * 8);
+  ScratchCarver c(base);
+  GridParams* prm = c.take<GridParams>(1, 256);
+  int* start = c.take<int>(cells + 2, 256);  // the cells, the overflow bucket, the end
+  int* cell = c.take<int>(k, 256);
+  int* rank = c.take<int>(k, 256);
+  int* sidx = c.take<int>(k, 256);
+  double* sx = c.take<double>(k, 256);
+  double* sy = c.take<double>(k, 256);
   if (s) *s = Scratch{prm, start, cell, rank, sidx, sx, sy};
-  return off;
+  return c.bytes();
 }
 
 __device__ __forceinline__ bool finite2(double x, double y) { return isfinite(x) && isfinite(y); }
@@ -386,13 +378,13 @@ extern "C" int sr_idw_interpolate(const double* pts2d, const float* z, int64_t k
   int64_t need = 0;
   if (sr_idw_grid_scratch(k, n_neighbors, &need)) return 1;
   SR_REQUIRE(pts2d && z && scratch && out, "sr_idw_interpolate: null pointer");
-  SR_REQUIRE(scratch_bytes >= need, "sr_idw_interpolate: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
+  if (require_scratch("sr_idw_interpolate", scratch_bytes, need)) return 1;
   int64_t nq;
   unsigned grid;
   if (query) {
     SR_REQUIRE(n_query >= 0 && n_query <= ((int64_t)1 << 36), "sr_idw_interpolate: n_query must be in 0..2^36 (got %lld)", (long long)n_query);
     nq = n_query;
-    grid = (unsigned)((nq + kThreads - 1) / kThreads);
+    grid = blocks_for(nq);
   } else {
     SR_REQUIRE(height >= 1 && width >= 1 && height <= 65536 && width <= 65536,
                "sr_idw_interpolate: the raster must be 1..65536 pixels on each side (got %d x %d)", height, width);
@@ -405,7 +397,7 @@ extern "C" int sr_idw_interpolate(const double* pts2d, const float* z, int64_t k
   scratch_layout(k, cells, scratch, &s);
   hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(kSetupThreads), 0, st, pts2d, k, cells, s.prm, s.start);
   if (check_launch("grid_setup_kernel")) return 2;
-  const unsigned kb = (unsigned)((k + kThreads - 1) / kThreads);
+  const unsigned kb = blocks_for(k);
   hipLaunchKernelGGL(count_kernel, dim3(kb), dim3(kThreads), 0, st, pts2d, k, cells, (const GridParams*)s.prm, s.start, s.cell, s.rank);
   if (check_launch("count_kernel")) return 2;
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kSetupThreads), 0, st, s.start, cells + 2);

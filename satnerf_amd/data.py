@@ -356,12 +356,8 @@ def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_d
     return out
 
 
-def colors_from_image(image, h, w, device="cuda", out=None, layout=None):
-    """The (h * w, 3) fp32 colour rows of one 8-bit RGB image on the GPU, as ``load_tensor_from_rgb_geotiff`` (datasets/satellite.py:
-    67-80) makes them: ``u8 / 255``, and the bicubic resize to h x w when that is not the image's own size (DESIGN.md section 7.7).
-    ``image``: a uint8 array or tensor, (H, W, 3) or (3, H, W), on the host or already on the device; the host uploads its 3 bytes per
-    pixel and ``ops.image_colors`` does the rest.  ``out``: (h * w, 3) fp32 rows on ``device`` to write into; ``layout``: "hwc" / "chw"
-    for an image whose shape reads both ways."""
+def _colors_on_device(op, what, image, h, w, device, out, layout):
+    """``ops.<op>`` of a uint8 image (array or tensor, host or device) uploaded to ``device``, with that device current."""
     import contextlib
 
     import numpy as np
@@ -370,10 +366,19 @@ def colors_from_image(image, h, w, device="cuda", out=None, layout=None):
 
     t = image if torch.is_tensor(image) else torch.from_numpy(np.require(np.asarray(image), requirements=["C", "W"]))
     if t.dtype != torch.uint8:
-        raise ValueError(f"image must be uint8 (8-bit colours), got {t.dtype}")
+        raise ValueError(f"image must be uint8 ({what}), got {t.dtype}")
     dev = torch.device(device)
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-        return ops.image_colors(t.to(dev).contiguous(), int(h), int(w), out=out, layout=layout)
+        return getattr(ops, op)(t.to(dev).contiguous(), int(h), int(w), out=out, layout=layout)
+
+
+def colors_from_image(image, h, w, device="cuda", out=None, layout=None):
+    """The (h * w, 3) fp32 colour rows of one 8-bit RGB image on the GPU, as ``load_tensor_from_rgb_geotiff`` (datasets/satellite.py:
+    67-80) makes them: ``u8 / 255``, and the bicubic resize to h x w when that is not the image's own size (DESIGN.md section 7.7).
+    ``image``: a uint8 array or tensor, (H, W, 3) or (3, H, W), on the host or already on the device; the host uploads its 3 bytes per
+    pixel and ``ops.image_colors`` does the rest.  ``out``: (h * w, 3) fp32 rows on ``device`` to write into; ``layout``: "hwc" / "chw"
+    for an image whose shape reads both ways."""
+    return _colors_on_device("image_colors", "8-bit colours", image, h, w, device, out, layout)
 
 
 def _read_image_pillow(path):
@@ -459,18 +464,7 @@ def blender_colors_from_image(image, h, w, device="cuda", out=None, layout=None)
     ``alpha > 0``.  ``image``: a uint8 array or tensor, (H, W, 4) or (4, H, W), on the host or already on the
     device; the host uploads its 4 bytes per pixel and ``ops.blender_colors`` does the rest.  ``out``: (h * w, 3) fp32 rows on ``device``
     to write the colours into; ``layout``: "hwc" / "chw" for an image whose shape reads both ways."""
-    import contextlib
-
-    import numpy as np
-
-    from . import ops
-
-    t = image if torch.is_tensor(image) else torch.from_numpy(np.require(np.asarray(image), requirements=["C", "W"]))
-    if t.dtype != torch.uint8:
-        raise ValueError(f"image must be uint8 (8-bit RGBA), got {t.dtype}")
-    dev = torch.device(device)
-    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-        return ops.blender_colors(t.to(dev).contiguous(), int(h), int(w), out=out, layout=layout)
+    return _colors_on_device("blender_colors", "8-bit RGBA", image, h, w, device, out, layout)
 
 
 def blender_rays(h, w, focal, c2w, near=2.0, far=6.0, device="cuda", out=None):

@@ -66,6 +66,13 @@ def _same_device(t, name):
                          "(wrap the call in torch.cuda.device(...) or torch.cuda.set_device)")
 
 
+def _scratch_bytes(entry, *args):
+    """What a ``*_scratch`` entry point answers for these integer sizes (host only)."""
+    nbytes = C.c_int64(0)
+    _lib.call(entry, *(int(a) for a in args), C.byref(nbytes))
+    return nbytes.value
+
+
 def _rows(t, name, min_cols):
     """A 2-D fp32 view whose rows may be strided (e.g. rays[:, 3:6]): returns (tensor, row stride in elements)."""
     if t.dim() != 2 or t.shape[1] < min_cols or t.dtype != torch.float32 or not t.is_cuda or t.stride(1) != 1:
@@ -466,9 +473,7 @@ def reprojection_errors(rpc, colrow, pts3d_idx, pts3d, out=None):
 
 def keypoint_weights_scratch(n_pts, n_cams):
     """Bytes of scratch sr_keypoint_weights needs (host only)."""
-    nbytes = C.c_int64(0)
-    _lib.call("sr_keypoint_weights_scratch", int(n_pts), int(n_cams), C.byref(nbytes))
-    return nbytes.value
+    return _scratch_bytes("sr_keypoint_weights_scratch", n_pts, n_cams)
 
 
 def keypoint_weights(pts3d_idx, cam, err, n_pts, n_cams, scratch=None):
@@ -871,9 +876,7 @@ CLOUD_MODES = {"min": 0, "max": 1, "avg": 2, "med": 3}
 
 def cloud_grid_scratch(n, map_w, map_h):
     """Bytes of scratch sr_cloud_grid needs for n points on a map_h x map_w grid (host only)."""
-    nbytes = C.c_int64(0)
-    _lib.call("sr_cloud_grid_scratch", int(n), int(map_w), int(map_h), C.byref(nbytes))
-    return nbytes.value
+    return _scratch_bytes("sr_cloud_grid_scratch", n, map_w, map_h)
 
 
 def cloud_grid(east, north, alt, x0, y0, definition, map_w, map_h, rule="nearest", mode="med", scratch=None, out=None, count=None,
@@ -936,10 +939,7 @@ def dsm_compute_shift(u, v, irange=5, scaling=True, out=None, scratch=None, maps
     u, v = _raster(u, "u"), _raster(v, "v")
     _same_device(v, "v")
     nbytes, levels = dsm_register_plan(u.shape, v.shape, irange)
-    if scratch is None:
-        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=u.device)
-    elif not (scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= nbytes):
-        raise ValueError(f"scratch must be a contiguous device tensor of >= {nbytes} bytes")
+    scratch = _metric_scratch(scratch, nbytes, u.device)
     out = torch.empty(9, dtype=torch.int64, device=u.device) if out is None else _chk(out, "out", torch.int64)
     n = 2 * int(irange) + 1
     ncc = torch.empty(levels, n, n, dtype=torch.float64, device=u.device) if maps else None
@@ -967,9 +967,7 @@ def dsm_apply_shift(v, shift, coef, out=None):
 # ---- tie-point interpolation (csrc/tie_points.hip) --------------------------------------------------------------------------------
 def idw_grid_scratch(k, n_neighbors):
     """Bytes of scratch sr_idw_interpolate needs for k points and n_neighbors (host only)."""
-    nbytes = C.c_int64(0)
-    _lib.call("sr_idw_grid_scratch", int(k), int(n_neighbors), C.byref(nbytes))
-    return nbytes.value
+    return _scratch_bytes("sr_idw_grid_scratch", k, n_neighbors)
 
 
 def idw_interpolate(pts2d, z, n_neighbors, query=None, height=0, width=0, want_indices=False, want_visited=False, out=None, scratch=None):
@@ -1028,9 +1026,7 @@ def gaussian_filter_f64(image, taps0, taps1, out=None, tmp=None):
 # ---- image metrics (csrc/image_metrics.hip) ---------------------------------------------------------------------------------------
 def image_metrics_scratch(n=0, planes=0, h=0, w=0):
     """Bytes of scratch sr_image_sse over n elements and sr_ssim_sum over (planes, h, w) need (host only)."""
-    nbytes = C.c_int64(0)
-    _lib.call("sr_image_metrics_scratch", int(n), int(planes), int(h), int(w), C.byref(nbytes))
-    return nbytes.value
+    return _scratch_bytes("sr_image_metrics_scratch", n, planes, h, w)
 
 
 def _metric_scratch(scratch, nbytes, dev):
@@ -1076,30 +1072,37 @@ def ssim_sum(img1, img2, out=None, scratch=None):
 
 
 # ---- a dataset's colours (csrc/image_colors.hip) ------------------------------------------------------------------------------------
+def _image_u8(image_u8, bands, layout):
+    """(h, w, (row, pixel, channel) byte strides) of a contiguous uint8 device image of ``bands`` bands, (H, W, bands) ("hwc") or
+    (bands, H, W) ("chw"); layout None reads it off the shape."""
+    b, word = bands, {3: "three", 4: "four"}[bands]
+    image_u8 = _chk(image_u8, "image_u8", torch.uint8)
+    if image_u8.dim() != 3:
+        raise ValueError(f"image_u8 must be (H, W, {b}) or ({b}, H, W), got {tuple(image_u8.shape)}")
+    if layout is None:
+        first, last = image_u8.shape[0] == b, image_u8.shape[2] == b
+        if first and last:
+            raise ValueError(f"image_u8 {tuple(image_u8.shape)} reads as (H, W, {b}) and as ({b}, H, W): pass layout='hwc' or layout='chw'")
+        if not (first or last):
+            raise ValueError(f"image_u8 must have {word} bands, (H, W, {b}) or ({b}, H, W), got {tuple(image_u8.shape)}")
+        layout = "chw" if first else "hwc"
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if image_u8.shape[0 if layout == "chw" else 2] != b:
+        raise ValueError(f"image_u8 {tuple(image_u8.shape)} does not have {word} bands in layout {layout!r}")
+    h, w = (image_u8.shape[1], image_u8.shape[2]) if layout == "chw" else (image_u8.shape[0], image_u8.shape[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"image_u8 must be at least 1 x 1, got {h} x {w}")
+    return h, w, ((w, 1, h * w) if layout == "chw" else (b * w, b, 1))
+
+
 def image_colors(image_u8, out_h, out_w, out=None, layout=None):
     """sr_image_colors: the (out_h * out_w, 3) fp32 colour rows of one 8-bit image, ``u8 / 255`` and -- unless (out_h, out_w) is the
     image's own size -- the bicubic resize of the reference's loader (datasets/satellite.py:67-80).  ``image_u8``: a contiguous uint8
     device tensor, (H, W, 3) (``layout="hwc"``) or (3, H, W) (``"chw"``); the layout is read off the shape, and a 3 x W x 3 image needs
     it said.  ``out`` = an (out_h * out_w, 3) fp32 tensor with contiguous rows to write into (e.g. one image's rows of a dataset's
     colour tensor).  Nothing is launched for an empty output."""
-    image_u8 = _chk(image_u8, "image_u8", torch.uint8)
-    if image_u8.dim() != 3:
-        raise ValueError(f"image_u8 must be (H, W, 3) or (3, H, W), got {tuple(image_u8.shape)}")
-    if layout is None:
-        first, last = image_u8.shape[0] == 3, image_u8.shape[2] == 3
-        if first and last:
-            raise ValueError(f"image_u8 {tuple(image_u8.shape)} reads as (H, W, 3) and as (3, H, W): pass layout='hwc' or layout='chw'")
-        if not (first or last):
-            raise ValueError(f"image_u8 must have three bands, (H, W, 3) or (3, H, W), got {tuple(image_u8.shape)}")
-        layout = "chw" if first else "hwc"
-    if layout not in ("hwc", "chw"):
-        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
-    if image_u8.shape[0 if layout == "chw" else 2] != 3:
-        raise ValueError(f"image_u8 {tuple(image_u8.shape)} does not have three bands in layout {layout!r}")
-    h, w = (image_u8.shape[1], image_u8.shape[2]) if layout == "chw" else (image_u8.shape[0], image_u8.shape[1])
-    if h < 1 or w < 1:
-        raise ValueError(f"image_u8 must be at least 1 x 1, got {h} x {w}")
-    strides = (w, 1, h * w) if layout == "chw" else (3 * w, 3, 1)
+    h, w, strides = _image_u8(image_u8, 3, layout)
     out_h, out_w = int(out_h), int(out_w)
     if out_h < 0 or out_w < 0:
         raise ValueError(f"out_h and out_w must be >= 0, got {out_h} and {out_w}")
@@ -1164,9 +1167,7 @@ def _lanczos_device(n_in, n_out, dev):
 
 def blender_colors_scratch(src_h, src_w, out_h, out_w):
     """Bytes of scratch sr_blender_colors needs for this resize (host only): the (src_h, out_w, 4) intermediate when both passes run."""
-    nbytes = C.c_int64(0)
-    _lib.call("sr_blender_colors_scratch", int(src_h), int(src_w), int(out_h), int(out_w), C.byref(nbytes))
-    return nbytes.value
+    return _scratch_bytes("sr_blender_colors_scratch", src_h, src_w, out_h, out_w)
 
 
 def blender_colors(image_u8, out_h, out_w, out=None, layout=None, want_rgba=False):
@@ -1176,24 +1177,7 @@ def blender_colors(image_u8, out_h, out_w, out=None, layout=None, want_rgba=Fals
     said.  Returns (rgbs (out_h * out_w, 3) fp32, valid_mask (out_h * out_w,) bool = alpha > 0), and with ``want_rgba`` also the resized
     image, (out_h, out_w, 4) uint8.  ``out`` = an (out_h * out_w, 3) fp32 tensor with contiguous rows to write the colours into.  Nothing
     is launched for an empty output."""
-    image_u8 = _chk(image_u8, "image_u8", torch.uint8)
-    if image_u8.dim() != 3:
-        raise ValueError(f"image_u8 must be (H, W, 4) or (4, H, W), got {tuple(image_u8.shape)}")
-    if layout is None:
-        first, last = image_u8.shape[0] == 4, image_u8.shape[2] == 4
-        if first and last:
-            raise ValueError(f"image_u8 {tuple(image_u8.shape)} reads as (H, W, 4) and as (4, H, W): pass layout='hwc' or layout='chw'")
-        if not (first or last):
-            raise ValueError(f"image_u8 must have four bands, (H, W, 4) or (4, H, W), got {tuple(image_u8.shape)}")
-        layout = "chw" if first else "hwc"
-    if layout not in ("hwc", "chw"):
-        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
-    if image_u8.shape[0 if layout == "chw" else 2] != 4:
-        raise ValueError(f"image_u8 {tuple(image_u8.shape)} does not have four bands in layout {layout!r}")
-    h, w = (image_u8.shape[1], image_u8.shape[2]) if layout == "chw" else (image_u8.shape[0], image_u8.shape[1])
-    if h < 1 or w < 1:
-        raise ValueError(f"image_u8 must be at least 1 x 1, got {h} x {w}")
-    strides = (w, 1, h * w) if layout == "chw" else (4 * w, 4, 1)
+    h, w, strides = _image_u8(image_u8, 4, layout)
     out_h, out_w = int(out_h), int(out_w)
     if out_h < 0 or out_w < 0:
         raise ValueError(f"out_h and out_w must be >= 0, got {out_h} and {out_w}")

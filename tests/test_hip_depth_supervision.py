@@ -110,6 +110,35 @@ def test_reprojection_errors_within_one_ulp_and_weights_repeatable():
     assert np.abs(w_got - np.exp(-(e_want / e_mean) ** 2)).max() <= 1e-6
 
 
+def test_keypoint_weights_with_more_partials_than_threads():
+    """n_pts = 65 537 gives 257 per-workgroup partials, so finalize's strided sum takes a second trip (the 50 000-point case has 196).
+    The same restatement and bounds as above, on random fp32 errors of 3 cameras, and two runs bit-equal."""
+    from satnerf_amd import ops
+
+    n_pts, n_cams, per_cam = 65_537, 3, 60_000
+    g = np.random.default_rng(11)
+    errs = [g.uniform(0.0, 2.0, per_cam).astype(np.float32) for _ in range(n_cams)]
+    idxs = [g.integers(0, n_pts, per_cam) for _ in range(n_cams)]  # with repeats
+    idxs[0][-1] = n_pts - 1  # the lone point of the last workgroup is observed
+    tss = [np.full(per_cam, t, np.int64) for t in range(n_cams)]
+    err, idx, ts = (torch.from_numpy(np.concatenate(a)).to(DEV) for a in (errs, idxs, tss))
+    runs = [ops.keypoint_weights(idx, ts, err, n_pts, n_cams) for _ in range(2)]
+    for a, b in zip(*runs):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    errmat = np.zeros((n_pts, n_cams), np.float32)
+    for t, (e, ix) in enumerate(zip(errs, idxs)):
+        errmat[ix, t] = e
+    e64 = np.zeros(n_pts)
+    for t in range(n_cams):
+        e64 += errmat[:, t]
+    e_want = e64.astype(np.float32)
+    e_mean = np.float32(e_want.astype(np.float64).sum() / n_pts)
+    e_got, w_got, em_got = (t.cpu().numpy() for t in runs[0])
+    print("e mismatches", int((e_got != e_want).sum()), "e_mean", em_got[0], e_mean, "max |dw|", np.abs(w_got - np.exp(-(e_want / e_mean) ** 2)).max())
+    assert np.array_equal(e_got, e_want) and em_got[0] == e_mean
+    assert np.abs(w_got - np.exp(-(e_want / e_mean) ** 2)).max() <= 1e-6
+
+
 def test_duplicate_observation_keeps_the_last():
     from satnerf_amd import ops
 

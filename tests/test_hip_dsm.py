@@ -208,6 +208,21 @@ def test_render_dsm_equals_dsm_from_depth_of_render_image_outputs():
     assert int(torch.isfinite(got.dsm).sum()) > 0
 
 
+def test_bounds_of_a_full_wave_plus_one_lane():
+    """n = 65: the 65th point sits alone in the second wave, whose other lanes carry the neutral keys through the shuffles.  It holds
+    the smallest easting; the largest easting belongs to a point whose altitude is NaN and must not count.  Exact against numpy."""
+    _, ops = _dsm()
+    g = np.random.default_rng(3)
+    east, north, alt = g.uniform(-5e5, 5e5, 65), g.uniform(-3e6, 3e6, 65), g.uniform(-50.0, 50.0, 65)
+    east[64], east[17], alt[17] = -6e5, 7e5, np.nan
+    north[40] = -0.0
+    ok = np.isfinite(alt)
+    got = ops.dsm_bounds(_d(east), _d(north), _d(alt)).cpu().numpy()
+    want = np.array([east[ok].min(), east[ok].max(), north[ok].min(), north[ok].max()])
+    assert ok.sum() == 64 and want[0] == -6e5 and want[1] < 7e5
+    assert np.array_equal(got.view(np.int64), want.view(np.int64)), (got, want)
+
+
 def test_edge_cases():
     dsm, _ = _dsm()
     rays, depth, center, scene_range, roi, heights = _scene(n_side=8)
