@@ -594,6 +594,56 @@ int sr_blender_colors(const uint8_t* src, int src_h, int src_w, int64_t row_stri
 int sr_pinhole_rays(int h, int w, float fx, float fy, float cx, float cy, const float* c2w, float near, float far, float* out,
                     void* stream);
 
+/* ---- evaluation image products: what study_solar_interpolation.py and train_utils.visualize_depth do to
+ * rendered images ---------------------------------------------------------------------------------------------------------------------
+ * Every image is DEVICE fp32 addressed as image[r * row_stride + c * col_stride] (strides in ELEMENTS, all >= 1): a dense (h, w) image
+ * is (w, 1), column k of the (N, 13) buffer of the image render is image + k with (13 w, 13), and a crop window starting at (r0, c0)
+ * is image + r0 * row_stride + c0 * col_stride with the window's sides.  The reference's window is rows int(h / 4) .. int(3 h / 4),
+ * columns int(w / 4) .. int(3 w / 4).  Every entry returns its errors (null pointers with a non-empty image, sides or strides out of
+ * range, a window that does not fit its strip, scratch too small or misaligned) before anything touches the device, launches nothing
+ * for an empty image, and does no host synchronisation: capturable.
+ *
+ * sr_nearest_fill: quickly_interpolate_nans_from_singlechannel_img (study_solar_interpolation.py:53-68), i.e. scipy's
+ * griddata(method="nearest"), on an (h, w) image with sides 0..8192.  A pixel is missing iff it is NaN (infinities and -0 are valid).
+ * out (h, w) dense fp32: a valid pixel is copied bit for bit; a missing pixel (r, c) takes the bits of the valid pixel (r', c') that
+ * minimises ((r - r')^2 + (c - c')^2, r', c') in lexicographic order -- the squared distance is an exact integer, and of several
+ * pixels at the least distance the one in the smallest row, then the smallest column, wins (scipy leaves that choice to its KD-tree).
+ * An image without a valid pixel comes back as it is, all NaN (scipy raises there).  index (optional, (h, w) int32, NULL to skip) =
+ * r' * w + c' of the pixel taken (a valid pixel's own position), -1 where there is none.  out must not overlap image.  scratch:
+ * caller-owned DEVICE bytes, 2-byte aligned, at least sr_nearest_fill_scratch (HOST only).  Two launches: a column pass (nearest
+ * valid row per pixel and column, ties to the upper row) and a row pass (minimum of the packed key over the row's columns).
+ *
+ * sr_colorize: train_utils.visualize_depth (train_utils.py:59-72) and hstack_dsm_tifs_v1 after its fill
+ * (study_solar_interpolation.py:85-93) over a (rows, cols) window, sides 0..65535.
+ *   1. nan_to_zero = 1 (visualize_depth's np.nan_to_num): NaN -> 0, +-inf -> +-FLT_MAX.  nan_to_zero = 0: values are taken as they are.
+ *   2. mi = vmin if bounds & 1 else the minimum over the window, ma = vmax if bounds & 2 else the maximum, both after step 1 and with
+ *      NaN skipped; held as integer keys, so no arrival order changes them (a window of NaN only: mi = +inf, ma = -inf).  With
+ *      bounds != 0, x is clipped: x < mi -> mi, then x > ma -> ma (a NaN stays).
+ *   3. q = (x - mi) / d, y = 255.0f * q, index = (uint8_t)y by truncation; each a single correctly rounded fp32 operation.  d =
+ *      (ma - mi) + 1e-8f, two rounded fp32 operations, unless bounds == 3: then d = denom, which the caller computes as the reference
+ *      does from two Python floats, (float)((double)vmax - (double)vmin + 1e-8).  (numpy 2 keeps a Python float weak beside an fp32
+ *      value, so with a measured bound the sum is fp32.)  Outside the reference's domain: a NaN or infinite y gives index 0, a finite
+ *      y is clamped to 0..255.
+ *   4. Outputs, any subset, NULL to skip: index_out (rows, cols) u8; strip: lut[index]'s three bytes at strip[(r * strip_cols +
+ *      strip_col0 + c) * 3 + k], a caller's (rows, strip_cols, 3) u8 image (this placement is the reference's np.hstack); chw (3, rows,
+ *      cols) fp32 = (float)lut[index][k] / 255.0f, torchvision's ToTensor and the expression of sr_image_colors.  lut: 256 x 3 DEVICE
+ *      bytes, in the channel order the caller wants out.
+ * scratch: 4-byte aligned DEVICE bytes, at least sr_colorize_scratch(bounds) (HOST only; 0 when both bounds are given).
+ *
+ * sr_unit_to_u8: hstack_sun_tifs / hstack_rgb_tifs (study_solar_interpolation.py:23-51): strip[(r * strip_cols + strip_col0 + c) *
+ * channels + k] = (uint8_t)(image[r * row_stride + c * col_stride + k * chan_stride] * 255.0f), one rounded multiply, then truncation;
+ * channels 1 or 3.  Composited sigmoid outputs lie in [0, 1]; outside it numpy's cast is undefined, and this kernel clamps to 0..255
+ * with NaN -> 0. */
+int sr_nearest_fill_scratch(int h, int w, int64_t* bytes);
+int sr_nearest_fill(const float* image, int h, int w, int64_t row_stride, int64_t col_stride, void* scratch, int64_t scratch_bytes,
+                    float* out, int32_t* index, void* stream);
+int sr_colorize_scratch(int bounds, int64_t* bytes);
+int sr_colorize(const float* image, int rows, int cols, int64_t row_stride, int64_t col_stride, int nan_to_zero, int bounds, float vmin,
+                float vmax, float denom, const uint8_t* lut, uint8_t* index_out, uint8_t* strip, int64_t strip_cols, int64_t strip_col0,
+                float* chw, void* scratch, int64_t scratch_bytes, void* stream);
+int sr_unit_to_u8(const float* image, int rows, int cols, int channels, int64_t row_stride, int64_t col_stride, int64_t chan_stride,
+                  uint8_t* strip, int64_t strip_cols, int64_t strip_col0, void* stream);
+
 /* ---- training-step kernels --------------------------------------------------------------
  * sr_satnerf_loss: metrics.SatNerfLoss for the coarse model (metrics.py:21-25,56-73): value = sum of
  * loss_parts[0 .. ceil(N/4)), and grad_scale * dLoss/d{rgb (N,3), weights (N,S), beta (N,S)} in g_*.

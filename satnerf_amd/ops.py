@@ -1216,3 +1216,103 @@ def pinhole_rays(h, w, fx, fy, cx, cy, c2w, near, far, out=None):
     _lib.call("sr_pinhole_rays", h, w, float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
               m.ctypes.data_as(C.POINTER(C.c_float)), float(np.float32(near)), float(np.float32(far)), _p(out), _stream())
     return out
+
+
+# ---- evaluation image products (csrc/image_products.hip) ----------------------------------------------------------------------------
+def _strided_image(t, name, dims):
+    """An fp32 device image read in place through its element strides (a column of the (N, 13) image buffer, a crop window): returns
+    the strides with those of one-element dimensions set to 1 (torch leaves them arbitrary; they are never stepped along)."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (got {t.device if torch.is_tensor(t) else type(t).__name__}); satnerf_amd has no CPU path")
+    _same_device(t, name)
+    if t.dtype != torch.float32 or t.dim() != dims:
+        raise ValueError(f"{name} must be a {dims}-D fp32 tensor, got {tuple(t.shape)} {t.dtype}")
+    strides = [1 if n <= 1 else s for n, s in zip(t.shape, t.stride())]
+    if min(strides) < 1:
+        raise ValueError(f"{name} must have positive strides, got {tuple(t.stride())}")
+    return strides
+
+
+def nearest_fill_scratch(h, w):
+    """Bytes of scratch sr_nearest_fill needs for an (h, w) image (host only)."""
+    return _scratch_bytes("sr_nearest_fill_scratch", h, w)
+
+
+def nearest_fill(image, want_index=False, out=None, scratch=None):
+    """sr_nearest_fill: the (h, w) fp32 image with every NaN replaced by the nearest non-NaN pixel's bits (squared Euclidean pixel
+    distance, ties to the smallest row, then column), the reference's griddata(method="nearest") hole fill.  ``image`` is read through
+    its strides.  Returns a new dense (h, w) tensor (or ``out``), and with ``want_index`` also the (h, w) int32 flat index r' * w + c' of
+    each pixel's source, -1 where the image has no valid pixel."""
+    rs, cs = _strided_image(image, "image", 2)
+    h, w = image.shape
+    out = torch.empty(h, w, dtype=torch.float32, device=image.device) if out is None else _chk(out, "out")
+    if tuple(out.shape) != (h, w):
+        raise ValueError(f"out must be ({h}, {w}), got {tuple(out.shape)}")
+    if h * w:  # the row pass reads source pixels while other workgroups write out
+        first, last = image.data_ptr(), image.data_ptr() + 4 * ((h - 1) * rs + (w - 1) * cs + 1)
+        if out.data_ptr() < last and first < out.data_ptr() + 4 * h * w:
+            raise ValueError("out must not overlap image")
+    index = torch.empty(h, w, dtype=torch.int32, device=image.device) if want_index else None
+    scratch = _metric_scratch(scratch, nearest_fill_scratch(h, w), image.device)
+    _lib.call("sr_nearest_fill", _p(image), h, w, rs, cs, _p(scratch), scratch.numel() * scratch.element_size(), _p(out), _p(index), _stream())
+    return (out, index) if want_index else out
+
+
+def colorize_denominator(vmin, vmax):
+    """The divisor the reference's ``ma - mi + 1e-8`` becomes when both bounds are Python floats: an fp64 sum, rounded to fp32 where it
+    meets the fp32 image."""
+    import numpy as np
+
+    return float(np.float32(float(vmax) - float(vmin) + 1e-8))
+
+
+def colorize(image, lut=None, nan_to_zero=False, vmin=None, vmax=None, want_index=False, strip=None, strip_col0=0, want_chw=False,
+             scratch=None):
+    """sr_colorize over the (rows, cols) fp32 image (read through its strides; pass a slice for a crop window): the byte index
+    ``(uint8)(255 * ((x - mi) / d))`` of the reference's depth colouring and ``lut[index]``.  ``vmin`` / ``vmax``: Python floats, or None
+    for the window's own minimum / maximum.  ``nan_to_zero``: visualize_depth's np.nan_to_num first.  Outputs: ``want_index`` -> (rows,
+    cols) uint8; ``strip`` -> the colours are written into this (rows, total_cols, 3) uint8 tensor from column ``strip_col0``;
+    ``want_chw`` -> (3, rows, cols) fp32 = byte / 255.  ``lut``: (256, 3) uint8 device tensor, needed for the coloured outputs.  Returns
+    {"index", "strip", "chw"} with the outputs asked for."""
+    import numpy as np
+
+    rs, cs = _strided_image(image, "image", 2)
+    rows, cols = image.shape
+    dev = image.device
+    if lut is not None and tuple(_chk(lut, "lut", torch.uint8).shape) != (256, 3):
+        raise ValueError(f"lut must be (256, 3) uint8, got {tuple(lut.shape)}")
+    if lut is None and (strip is not None or want_chw):
+        raise ValueError("a coloured output needs a lut")
+    if not (want_index or want_chw or strip is not None):
+        raise ValueError("no output requested")
+    if strip is not None:
+        if _chk(strip, "strip", torch.uint8).dim() != 3 or strip.shape[0] != rows or strip.shape[2] != 3:
+            raise ValueError(f"strip must be ({rows}, total_cols, 3) uint8, got {tuple(strip.shape)}")
+        if not 0 <= int(strip_col0) <= strip.shape[1] - cols:
+            raise ValueError(f"columns {strip_col0}..{int(strip_col0) + cols} do not fit a strip of {strip.shape[1]} columns")
+    bounds = (vmin is not None) | ((vmax is not None) << 1)
+    lo = float(np.float32(vmin)) if vmin is not None else 0.0
+    hi = float(np.float32(vmax)) if vmax is not None else 0.0
+    denom = colorize_denominator(vmin, vmax) if bounds == 3 else 0.0
+    index = torch.empty(rows, cols, dtype=torch.uint8, device=dev) if want_index else None
+    chw = torch.empty(3, rows, cols, dtype=torch.float32, device=dev) if want_chw else None
+    nbytes = _scratch_bytes("sr_colorize_scratch", bounds)
+    scratch = _metric_scratch(scratch, nbytes, dev) if nbytes else None
+    _lib.call("sr_colorize", _p(image), rows, cols, rs, cs, int(bool(nan_to_zero)), bounds, lo, hi, denom, _p(lut), _p(index), _p(strip),
+              0 if strip is None else strip.shape[1], int(strip_col0), _p(chw), _p(scratch), nbytes, _stream())
+    return {"index": index, "strip": strip, "chw": chw}
+
+
+def unit_to_u8(image, strip, strip_col0=0):
+    """sr_unit_to_u8: ``(uint8)(x * 255)`` of the (rows, cols, C) fp32 image (C = 1 or 3, read through its strides) into columns
+    ``strip_col0 ..`` of ``strip``, a contiguous (rows, total_cols, C) uint8 device tensor."""
+    rs, cs, ks = _strided_image(image, "image", 3)
+    rows, cols, ch = image.shape
+    if ch not in (1, 3):
+        raise ValueError(f"image must have 1 or 3 channels, got {ch}")
+    if _chk(strip, "strip", torch.uint8).dim() != 3 or strip.shape[0] != rows or strip.shape[2] != ch:
+        raise ValueError(f"strip must be ({rows}, total_cols, {ch}) uint8, got {tuple(strip.shape)}")
+    if not 0 <= int(strip_col0) <= strip.shape[1] - cols:
+        raise ValueError(f"columns {strip_col0}..{int(strip_col0) + cols} do not fit a strip of {strip.shape[1]} columns")
+    _lib.call("sr_unit_to_u8", _p(image), rows, cols, ch, rs, cs, ks, _p(strip), strip.shape[1], int(strip_col0), _stream())
+    return strip
