@@ -473,6 +473,29 @@ int sr_dsm_rasterize(const double* east, const double* north, const double* alt,
                      double resolution, int xsize, int ysize, int radius, double sigma, uint64_t* acc, float* dsm, float* weight,
                      void* stream);
 
+/* ---- nadir DSM: eval_s2p.lonlat_from_utm (eval_s2p.py:37-44) and one vertical ray per DSM cell ---------------
+ * sr_utm_to_latlon: the inverse of sr_utm_from_latlon for a given zone (1..60): east / north metres (N,) DEVICE fp64 -> lat / lon
+ * degrees (N,) DEVICE fp64 by Krueger's inverse series to n^6 (Karney 2011 eqs. 11, 15) and a fixed six Newton steps from the
+ * conformal to the geodetic latitude (eqs. 19-21); WGS84, k0 0.9996, false easting 500 km, false northing 0 in both hemispheres
+ * (southern points carry negative northings, as sr_utm_from_latlon writes them).  lon = central meridian + an angle in (-180, 180],
+ * not wrapped.  A non-finite east or north gives NaN lat and lon.  n <= 0 launches nothing.
+ * sr_ortho_rays: get_rays + normalize_rays (datasets/satellite.py:18-65,218-227) for a camera that looks straight down every cell of
+ * a DSM grid, the RPC localisation replaced by the grid's own lon / lat.  Cell i = (row j = i / xsize, column c = i % xsize), row 0
+ * at the top (sr_dsm_rasterize's layout); its centre E = xoff + (c + 0.5) r, N = yoff - (j + 0.5) r; (phi, lambda) = sr_utm_to_latlon
+ * of (E, N).  Row i of rays (DEVICE fp32, row_stride >= 11 floats between rows, columns beyond 10 untouched):
+ *   0..2  origin (ECEF(phi, lambda, max_alt) - center) / range, evaluated in fp64 and rounded to fp32 ONCE (the reference casts the
+ *         ECEF origin to fp32 before subtracting the centre: ~0.4 m of error this does not have)
+ *   3..5  direction -(cos phi cos lambda, cos phi sin lambda, sin phi), the inward ellipsoid normal in closed form
+ *   6, 7  near = 0, far = (max_alt - min_alt) / range
+ *   8..10 sun_d (3 HOST floats) as given
+ * so the point at depth t along ray i has altitude max_alt - t range over the cell centre.  center = 3 HOST doubles.  latlon
+ * (xsize * ysize, 2) DEVICE fp64 = (lat, lon) degrees per cell, may be NULL.  Errors (nothing is launched): zone outside 1..60,
+ * min_alt >= max_alt, range <= 0, resolution <= 0, xsize or ysize < 1, xsize * ysize >= 2^31, row_stride < 11, any of them not
+ * finite.  Neither entry synchronises with the host: capturable. */
+int sr_utm_to_latlon(const double* east, const double* north, int64_t n, int zone, double* lat, double* lon, void* stream);
+int sr_ortho_rays(double xoff, double yoff, double resolution, int xsize, int ysize, int zone, double min_alt, double max_alt,
+                  const double* center, double range, const float* sun_d, float* rays, int row_stride, double* latlon, void* stream);
+
 /* ---- cloud fusion: eval_s2p.project_cloud_into_utm_grid (eval_s2p.py:175-226) ---------------------------------
  * sr_cloud_grid bins a UTM cloud (east / north / alt (N,) DEVICE fp64, sr_depth_to_utm's outputs) into a map_h x map_w grid and keeps
  * per cell the min (mode 0), max (1), mean (2) or median (3) of the altitudes that landed in it: out (map_h, map_w) DEVICE fp64, NaN

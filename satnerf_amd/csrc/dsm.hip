@@ -5,7 +5,7 @@
 
 #include "block_device.h"
 #include "common.h"
-#include "geo_device.h"
+#include "geo_device.h"  // utm_forward (and its inverse), the ECEF <-> geodetic pair
 
 namespace sr {
 
@@ -29,42 +29,6 @@ __host__ __device__ inline int utm_zone_number(double lat, double lon) {
 __host__ __device__ inline int utm_zone_letter(double lat) {
   if (!(lat >= -80 && lat <= 84)) return 0;
   return "CDEFGHJKLMNPQRSTUVWXX"[(int)(lat + 80) >> 3];
-}
-
-// ---- transverse Mercator, Krueger's series to order n^6 (Karney 2011, eqs. 7-9, 11, 35), WGS84 ---------------------------------
-// UTM scale k0 = 0.9996, false easting 500 km, false northing 0 in BOTH hemispheres: the reference's "+proj=utm +zone=<n><L>"
-// carries no +south, so southern points get negative northings.  Series truncation error < 5e-9 m within 3900 km of the
-// central meridian (Karney 2011, section 4), i.e. far below the fp64 rounding of the inputs here.
-__device__ inline void utm_forward(double lat_deg, double lon_deg, int zone, double& east, double& north) {
-  const double kDeg = 3.141592653589793 / 180;
-  const double a = 6378137.0, f = 1 / 298.257223563;
-  const double e = sqrt(f * (2 - f));
-  const double n = f / (2 - f), n2 = n * n, n3 = n2 * n, n4 = n3 * n, n5 = n4 * n, n6 = n5 * n;
-  const double A = a / (1 + n) * (1 + n2 / 4 + n4 / 64 + n6 / 256);
-  const double alpha[6] = {
-      n / 2 - 2 * n2 / 3 + 5 * n3 / 16 + 41 * n4 / 180 - 127 * n5 / 288 + 7891 * n6 / 37800,
-      13 * n2 / 48 - 3 * n3 / 5 + 557 * n4 / 1440 + 281 * n5 / 630 - 1983433 * n6 / 1935360,
-      61 * n3 / 240 - 103 * n4 / 140 + 15061 * n5 / 26880 + 167603 * n6 / 181440,
-      49561 * n4 / 161280 - 179 * n5 / 168 + 6601661 * n6 / 7257600,
-      34729 * n5 / 80640 - 3418889 * n6 / 1995840,
-      212378941 * n6 / 319334400};
-  double dl = lon_deg - (6.0 * zone - 183.0);  // longitude from the central meridian, wrapped to [-180, 180)
-  if (dl >= 180) dl -= 360;
-  if (dl < -180) dl += 360;
-  const double lam = dl * kDeg, phi = lat_deg * kDeg;
-  const double tau = tan(phi);
-  const double sig = sinh(e * atanh(e * tau / sqrt(1 + tau * tau)));
-  const double taup = tau * sqrt(1 + sig * sig) - sig * sqrt(1 + tau * tau);  // tangent of the conformal latitude
-  const double cl = cos(lam);
-  const double xip = atan2(taup, cl);
-  const double etap = asinh(sin(lam) / sqrt(taup * taup + cl * cl));
-  double xi = xip, eta = etap;
-  for (int j = 1; j <= 6; ++j) {
-    xi += alpha[j - 1] * sin(2 * j * xip) * cosh(2 * j * etap);
-    eta += alpha[j - 1] * cos(2 * j * xip) * sinh(2 * j * etap);
-  }
-  east = 500000.0 + 0.9996 * A * eta;
-  north = 0.9996 * A * xi;
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "geo_device.h"
 
 namespace sr {
 
@@ -63,17 +64,6 @@ __device__ __forceinline__ void rpc_project(const RpcModel& m, double lon, doubl
   const double x = (lat - m.lat_offset) / m.lat_scale, y = (lon - m.lon_offset) / m.lon_scale, z = (alt - m.alt_offset) / m.alt_scale;
   col = rpc_poly(m.col_num, x, y, z) / rpc_poly(m.col_den, x, y, z) * m.col_scale + m.col_offset;
   row = rpc_poly(m.row_num, x, y, z) / rpc_poly(m.row_den, x, y, z) * m.row_scale + m.row_offset;
-}
-
-__device__ __forceinline__ void geodetic_to_ecef(double lat, double lon, double alt, double& X, double& Y, double& Z) {
-#pragma clang fp contract(off)
-  const double rad_lat = lat * (3.141592653589793 / 180.0), rad_lon = lon * (3.141592653589793 / 180.0);
-  const double a = 6378137.0, f = 1 / 298.257223563;
-  const double e2 = 1 - (1 - f) * (1 - f);
-  const double v = a / sqrt(1 - e2 * sin(rad_lat) * sin(rad_lat));
-  X = (v + alt) * cos(rad_lat) * cos(rad_lon);
-  Y = (v + alt) * cos(rad_lat) * sin(rad_lon);
-  Z = (v * (1 - e2) + alt) * sin(rad_lat);
 }
 
 // get_rays (datasets/satellite.py:18-65) of one image point (col, row): localised at max_alt (ray origin) and min_alt, converted to

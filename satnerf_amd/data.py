@@ -160,6 +160,49 @@ def rays_from_rpc(rpc, height, width, min_alt, max_alt, center, scene_range, sun
     return rays
 
 
+def _ortho_grid(grid):
+    """(xoff, yoff, xsize, ysize, resolution) of a DSM grid as ``dsm.grid_from_roi`` returns it, checked."""
+    vals = list(grid)
+    if len(vals) != 5:
+        raise ValueError(f"grid must hold (xoff, yoff, xsize, ysize, resolution), got {len(vals)} values")
+    xoff, yoff, xsize, ysize, r = float(vals[0]), float(vals[1]), int(vals[2]), int(vals[3]), float(vals[4])
+    if xsize < 1 or ysize < 1 or not r > 0:
+        raise ValueError(f"zero-size DSM grid {tuple(vals)}")
+    return xoff, yoff, xsize, ysize, r
+
+
+def ortho_rays(grid, zone, min_alt, max_alt, center, scene_range, sun_d, device="cuda", out=None, return_latlon=False):
+    """The (ysize * xsize, 11) fp32 ray block of a nadir camera over a DSM grid, on the GPU (csrc/ortho.hip):
+    one ray straight down through the centre of every cell, row-major with row 0 at the top (``dsm.DSM``'s layout), so
+    ``x.view(ysize, xsize, -1)`` of any per-ray output is its ortho image.  It is ``get_rays`` + ``normalize_rays``
+    (datasets/satellite.py:18-65,218-227) with the RPC localisation replaced by the inverse UTM projection of the cell centre.
+
+    ``grid`` = (xoff, yoff, xsize, ysize, resolution), e.g. ``dsm.grid_from_roi(roi)``; ``zone`` 1..60 or e.g. "17R" (false northing 0
+    in both hemispheres, as everywhere here); ``min_alt`` < ``max_alt`` the altitude bounds of the scene; ``center`` (3,) /
+    ``scene_range`` its ECEF normalisation; ``sun_d`` the (3,) sun direction every ray carries (``data.sun_direction``).  The origin sits
+    at ``max_alt`` and is normalised in fp64 before its one rounding to fp32; near = 0, far = (max_alt - min_alt) / scene_range, so depth
+    t means altitude max_alt - t * scene_range.  ``out``: a (ysize * xsize, >=11) fp32 device tensor whose columns 0..10 are written
+    (e.g. a wider image buffer).  With ``return_latlon`` the result is (rays, latlon (ysize * xsize, 2) fp64 (lat, lon) degrees)."""
+    from . import dsm, ops
+
+    xoff, yoff, xsize, ysize, r = _ortho_grid(grid)
+    dev = torch.device(device)
+    if dev.type != "cuda" or (out is not None and not (torch.is_tensor(out) and out.is_cuda)):
+        raise ValueError("ortho_rays runs on the GPU: satnerf_amd has no CPU path")
+    if not float(min_alt) < float(max_alt):
+        raise ValueError(f"need min_alt < max_alt, got {min_alt} and {max_alt}")
+    if not float(scene_range) > 0:
+        raise ValueError(f"scene_range must be > 0, got {scene_range}")
+    sun = [float(v) for v in (sun_d.tolist() if hasattr(sun_d, "tolist") else sun_d)]
+    if len(sun) != 3:
+        raise ValueError(f"sun_d must hold 3 values, got {len(sun)}")
+    ctr = [float(v) for v in (center.tolist() if hasattr(center, "tolist") else center)]
+    rays, latlon = ops.ortho_rays(xoff, yoff, r, xsize, ysize, dsm._zone_number(zone), min_alt, max_alt, ctr, scene_range, sun, dev, out=out,
+                                  want_latlon=return_latlon)
+    rays = rays[:, :11]  # a wider ``out`` keeps its other columns to itself
+    return (rays, latlon) if return_latlon else rays
+
+
 def read_scene_loc(root_dir):
     """(center (3,) fp32 tensor, scene_range float) from ``root_dir/scene.loc`` as ``SatelliteDataset.__init__`` loads them
     (datasets/satellite.py:108-110): both rounded to fp32 (``scene_range`` is the fp32 maximum of the three scales, returned as a

@@ -6,6 +6,8 @@ their names and argument order; geometry is fp64, the rasteriser is the HIP kern
 and writing stay with the caller (``DSM.transform`` is the affine the reference writes).  The reference's dsmr registration
 (``compute_shift`` / ``apply_shift``, numba on the CPU there) is the HIP search of csrc/dsm_register.hip.  Several clouds fuse into
 one DSM by a per-cell median / mean / min / max (``eval_s2p.project_cloud_into_utm_grid``; csrc/cloud_grid.hip, section 7.6).
+A nadir DSM needs neither cloud nor splat: one vertical ray per cell of a UTM grid (``render_ortho_dsm``; csrc/ortho.hip, section 7.11),
+whose inverse projection is also ``eval_s2p.lonlat_from_utm``.
 
 The rasteriser follows this project's own grid / splat convention (include/satrender.h, sr_dsm_rasterize).  plyflatten cannot be
 run here, so parity with it is not claimed.
@@ -75,6 +77,16 @@ def utm_from_latlon(lats, lons, zone=None):
             raise ValueError("no points: the UTM zone comes from the first point")
         zone = utm_zone(lats[0].item(), lons[0].item())[0]
     return ops.utm_from_latlon(lats, lons, _zone_number(zone))
+
+
+def lonlat_from_utm(easts, norths, zone):
+    """``eval_s2p.lonlat_from_utm`` (eval_s2p.py:37-44) on the GPU: (lons, lats) fp64 device tensors in degrees -- the reference's
+    name and return order -- of UTM eastings / northings in ``zone`` (1..60 or e.g. "17R"), the inverse of :func:`utm_from_latlon`
+    (csrc/ortho.hip).  False northing is 0 in both hemispheres: southern points carry negative northings."""
+    if not (torch.is_tensor(easts) and torch.is_tensor(norths) and easts.is_cuda and norths.is_cuda):
+        raise ValueError("easts / norths must be GPU tensors: satnerf_amd has no CPU path")
+    lats, lons = ops.utm_to_latlon(easts.reshape(-1).double(), norths.reshape(-1).double(), _zone_number(zone))
+    return lons, lats
 
 
 @dataclasses.dataclass
@@ -218,17 +230,6 @@ def dsm_mae(pred, gt, gt_mask=None, register="z"):
         raise ValueError(f"gt_mask {tuple(gt_mask.shape)} does not match gt {tuple(gt.shape)}")
     if register == "xyz":
         return _dsm_mae_xyz(pred, gt, gt_mask)
-    if isinstance(pred, DSM):
-        if pred.roi is None:
-            raise ValueError("pred was not built on the ROI grid: call dsm_from_depth(..., roi=...) (cropping is not implemented)")
-        pred = pred.dsm
-    for name, t in (("pred", pred), ("gt", gt), ("gt_mask", gt_mask)):
-        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
-            raise ValueError(f"{name} must be a GPU tensor: satnerf_amd has no CPU path")
-    if pred.shape != gt.shape or pred.dim() != 2:
-        raise ValueError(f"pred {tuple(pred.shape)} is not on the ground truth's (H, W) grid {tuple(gt.shape)}")
-    if gt_mask is not None and gt_mask.shape != gt.shape:
-        raise ValueError(f"gt_mask {tuple(gt_mask.shape)} does not match gt {tuple(gt.shape)}")
     p, g = pred.double().clone(), gt.to(pred.device).double()
     if gt_mask is not None:
         p[gt_mask == 9] = float("nan")
@@ -357,3 +358,70 @@ def render_dsm(models, rays, ts, args, center, scene_range, **dsm_kwargs):
     with torch.no_grad():
         depth = render_image_outputs(models, rays, ts, args)["depth"]
     return dsm_from_depth(rays, depth, center, scene_range, **dsm_kwargs)
+
+
+# ---- nadir DSM -----------------------------------------------------------------------------------------------
+def ortho_dsm_from_depth(depth, grid, max_alt, scene_range, zone="", roi=None):
+    """The :class:`DSM` of the depths rendered along ``data.ortho_rays(grid, ...)``: one altitude per cell, no cloud and no splat.
+    ``depth`` holds ysize * xsize values in grid order on the GPU; alt = max_alt - float64(depth) * scene_range, stored as fp32, NaN
+    where the depth is not finite; ``weight`` is 1 where the cell is valid and 0 elsewhere.  ``grid`` = (xoff, yoff, xsize, ysize,
+    resolution); ``roi`` (the ``{aoi}_DSM.txt`` array the grid came from) is recorded so that :func:`dsm_mae` takes the result."""
+    from .data import _ortho_grid
+
+    xoff, yoff, xsize, ysize, r = _ortho_grid(grid)
+    if not (torch.is_tensor(depth) and depth.is_cuda):
+        raise ValueError("depth must be a GPU tensor: satnerf_amd has no CPU path")
+    if depth.numel() != xsize * ysize:
+        raise ValueError(f"depth must hold one value per cell of the {ysize} x {xsize} grid, got {tuple(depth.shape)}")
+    d = depth.reshape(ysize, xsize).to(torch.float64)
+    valid = torch.isfinite(d)
+    alt = torch.where(valid, float(max_alt) - d * float(scene_range), float("nan")).to(torch.float32)
+    return DSM(alt, valid.to(torch.float32), xoff, yoff, r, str(zone), None if roi is None else tuple(float(v) for v in roi))
+
+
+def _zone_of_center(center, device):
+    """(number, letter) of the UTM zone the scene centre (ECEF) lies in, through the ECEF -> geodetic kernel (one small read-back)."""
+    ray = torch.zeros(1, 6, dtype=torch.float32, device=device)
+    lat, lon, _ = ops.latlonalt_from_depth(ray, torch.zeros(1, dtype=torch.float32, device=device), center, 1.0)
+    return utm_zone(*torch.stack([lat[0], lon[0]]).cpu().tolist())
+
+
+def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, sun_d, roi=None, grid=None, zone=None):
+    """Render a nadir DSM of a trained field: ``data.ortho_rays`` over the grid -> ``render_image_outputs`` (once, no grad) ->
+    :func:`ortho_dsm_from_depth`.  Every cell gets exactly one altitude, sampled along its own vertical, so the raster has no holes
+    behind leaning buildings and involves no splat convention.
+
+    Exactly one of ``roi`` (the ``{aoi}_DSM.txt`` array (x, y, s, r), see :func:`grid_from_roi`) and ``grid`` (xoff, yoff, xsize,
+    ysize, resolution) sizes the raster.  ``ts``: an int (one transient-embedding index for every ray) or an (ysize * xsize,) tensor.
+    ``center`` / ``scene_range`` / ``min_alt`` / ``max_alt``: the scene's ECEF normalisation and altitude bounds; ``sun_d``: the sun
+    direction of the render.  ``zone`` (1..60 or "17R") defaults to the zone of the scene centre.
+
+    Returns (DSM, outputs).  ``outputs`` is the dict of ``render_image_outputs``; its per-ray tensors are in grid order, so
+    ``outputs["rgb"].view(ysize, xsize, 3)`` is the true-ortho colour image, and likewise "albedo" (.., 3), "sun" (.., 1), "beta" (.., 1),
+    "depth" / "acc" (ysize, xsize).  Cells outside the footprint the field was trained on are extrapolation: no footprint or visibility
+    mask is built."""
+    from .data import _ortho_grid, ortho_rays
+    from .rendering import render_image_outputs
+
+    if (roi is None) == (grid is None):
+        raise ValueError("exactly one of roi= and grid= sizes the DSM")
+    grid = _ortho_grid(grid_from_roi(roi) if roi is not None else grid)
+    t0 = models["t"].weight if hasattr(models["t"], "weight") else models["t"]
+    if not (torch.is_tensor(t0) and t0.is_cuda):
+        raise ValueError("the models must live on the GPU: satnerf_amd has no CPU path")
+    dev = t0.device
+    with torch.cuda.device(dev):
+        if zone is None:
+            number, letter = _zone_of_center(center, dev)
+            zone = zone_string(number, letter)
+        n = grid[2] * grid[3]
+        if torch.is_tensor(ts):
+            if ts.numel() != n:
+                raise ValueError(f"ts must be an int or hold one index per cell ({n}), got {tuple(ts.shape)}")
+            ts = ts.to(dev)
+        else:
+            ts = torch.full((n,), int(ts), dtype=torch.int64, device=dev)
+        rays = ortho_rays(grid, zone, min_alt, max_alt, center, scene_range, sun_d, device=dev)
+        with torch.no_grad():
+            outputs = render_image_outputs(models, rays, ts, args)
+        return ortho_dsm_from_depth(outputs["depth"], grid, max_alt, scene_range, zone=str(zone), roi=roi), outputs

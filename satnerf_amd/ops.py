@@ -869,6 +869,39 @@ def dsm_rasterize(east, north, alt, xoff, yoff, resolution, xsize, ysize, radius
     return dsm, weight
 
 
+# ---- nadir DSM rays (csrc/ortho.hip) -------------------------------------------------------------------------------------------------
+def utm_to_latlon(easts, norths, zone):
+    """(lat, lon) fp64 device tensors (degrees) of fp64 device east / north (metres) in UTM zone ``zone`` (1..60): sr_utm_to_latlon."""
+    easts, norths = _chk(easts.contiguous(), "easts", torch.float64), _chk(norths.contiguous(), "norths", torch.float64)
+    if easts.dim() != 1 or easts.shape != norths.shape:
+        raise ValueError(f"easts / norths must be two (N,) tensors, got {tuple(easts.shape)} / {tuple(norths.shape)}")
+    out = torch.empty(2, easts.shape[0], dtype=torch.float64, device=easts.device)
+    _lib.call("sr_utm_to_latlon", _p(easts), _p(norths), easts.shape[0], int(zone), out[0].data_ptr(), out[1].data_ptr(), _stream())
+    return out[0], out[1]
+
+
+def ortho_rays(xoff, yoff, resolution, xsize, ysize, zone, min_alt, max_alt, center, scene_range, sun_d, device="cuda", out=None,
+               want_latlon=False):
+    """sr_ortho_rays: one vertical ray per cell of the (ysize, xsize) DSM grid, row-major with row 0 at the top.  Returns (rays, latlon):
+    rays = ``out`` (a (ysize * xsize, >=11) fp32 tensor on ``device`` with unit inner stride, columns 0..10 written) or a new
+    (ysize * xsize, 11) tensor; latlon = (ysize * xsize, 2) fp64 (lat, lon) degrees, or None."""
+    n = int(xsize) * int(ysize)
+    dev = torch.device(device)
+    ctr = (C.c_double * 3)(*[float(v) for v in center])
+    sun = (C.c_float * 3)(*[float(v) for v in sun_d])
+    with torch.cuda.device(dev):
+        if out is None:
+            rays, stride = torch.empty(max(n, 0), 11, dtype=torch.float32, device=dev), 11
+        else:
+            rays, stride = _rows(out, "out", 11)
+            if rays.shape[0] != n:
+                raise ValueError(f"out must hold {n} rows (ysize * xsize), got {tuple(rays.shape)}")
+        latlon = torch.empty(max(n, 0), 2, dtype=torch.float64, device=dev) if want_latlon else None
+        _lib.call("sr_ortho_rays", float(xoff), float(yoff), float(resolution), int(xsize), int(ysize), int(zone), float(min_alt),
+                  float(max_alt), C.addressof(ctr), float(scene_range), sun, _p(rays), int(stride), _p(latlon), _stream())
+    return rays, latlon
+
+
 # ---- cloud fusion (csrc/cloud_grid.hip) --------------------------------------------------------------------------------------------
 CLOUD_RULES = {"nearest": 0, "floor": 1}
 CLOUD_MODES = {"min": 0, "max": 1, "avg": 2, "med": 3}
