@@ -44,12 +44,8 @@ from __future__ import annotations
 import os
 import sys
 
-A0 = 256                     # unified register numbering: 0..255 = v, 256..511 = a (the 512-wide kernel: one wave per SIMD, both files)
-
-
-def rn(r, n=1):
-    f, i = ("v", r) if r < A0 else ("a", r - A0)
-    return f"{f}{i}" if n == 1 else f"{f}[{i}:{i + n - 1}]"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from stream_common import A0, Ins, rn  # noqa: E402  (unified register numbering: the 512-wide kernel uses both files, one wave per SIMD)
 
 
 class Geo:
@@ -109,13 +105,6 @@ class Geo:
 
 S_SEL = ("s84", "s85", "s86", "s87")     # v_perm selectors of phase byte k: the byte lands in bits 8..15 of 0x43000000 (codec8.h phase8_rev)
 S_B4A, S_B4B, S_MAX = "s88", "s89", "s90"  # bytes4() selectors (codec8.h), the wave maximum
-
-
-class Ins:
-    __slots__ = ("op", "a", "text")
-
-    def __init__(self, op, a, text):
-        self.op, self.a, self.text = op, a, text
 
 
 class Trunk:
