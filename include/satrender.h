@@ -609,13 +609,26 @@ int sr_image_colors(const uint8_t* src, int src_h, int src_w, int64_t row_stride
  * [o (3), d (3), near, far], 16-byte aligned, pixel (r, c) at row r * w + c.  fx, fy, cx, cy, near, far and c2w (HOST, 12 floats, row-major
  * (3, 4) = [R | o]) are fp32 as the reference's tensors hold them.  Per pixel in fp64, every operation rounded: dx = (c - cx) / fx, dy =
  * -((r - cy) / fy), dz = -1, w_k = (dx R[k][0] + dy R[k][1]) + dz R[k][2], n = sqrt((w_0^2 + w_1^2) + w_2^2), d_k = w_k / n rounded to
- * fp32 once; o = c2w[:, 3].  h * w == 0 launches nothing.  No scratch, no host synchronisation: capturable. */
+ * fp32 once; o = c2w[:, 3].  h * w == 0 launches nothing.  No scratch, no host synchronisation: capturable.
+ * sr_blender_perturb: add_perturbation (datasets/blender.py:61-79) of one RGBA image, in front of sr_blender_colors.  src and dst: DEVICE
+ * bytes of (h, w) images addressed with the same three byte strides as above (each 1..2^40); dst may be src (in place) or must not
+ * overlap it.
+ * Per pixel: every band's byte v becomes lut[k * 256 + v] (lut: HOST, 4 x 256 bytes, NULL = unchanged), then for i = 0 .. n_rects - 1 in
+ * order a pixel with x0 <= c <= x1 and y0 <= r <= y1 (rects: HOST (n_rects, 4) int32 [x0, y0, x1, y1], both corners inside, any
+ * integers: a rectangle is clipped to the image, one outside it or with x1 < x0 or y1 < y0 draws nothing) takes the four bytes
+ * fills[4 i ..] (HOST (n_rects, 4) u8, RGBA); a later rectangle wins.  n_rects 0..16; rects and fills may be NULL when it is 0.  The
+ * table and the rectangles are copied into the kernel's arguments: no upload, the host arrays are free on return.  One launch; a dense
+ * 4-byte-aligned HWC image moves as one dword per pixel, anything else as bytes, with the same result.  Errors (null image, sides
+ * outside 1..65536, strides outside 1..2^40, n_rects out of range, null rects or fills with n_rects > 0, partial overlap) return before anything
+ * touches the device.  No scratch, no host synchronisation: capturable. */
 int sr_blender_colors_scratch(int src_h, int src_w, int out_h, int out_w, int64_t* bytes);
 int sr_blender_colors(const uint8_t* src, int src_h, int src_w, int64_t row_stride, int64_t pix_stride, int64_t chan_stride, int out_h,
                       int out_w, const int32_t* coef_w, int ksize_w, const int32_t* coef_h, int ksize_h, void* scratch,
                       int64_t scratch_bytes, float* rgbs, uint8_t* valid_mask, uint8_t* rgba, int stages, void* stream);
 int sr_pinhole_rays(int h, int w, float fx, float fy, float cx, float cy, const float* c2w, float near, float far, float* out,
                     void* stream);
+int sr_blender_perturb(const uint8_t* src, uint8_t* dst, int h, int w, int64_t row_stride, int64_t pix_stride, int64_t chan_stride,
+                       const uint8_t* lut, const int32_t* rects, const uint8_t* fills, int n_rects, void* stream);
 
 /* ---- evaluation image products: what study_solar_interpolation.py and train_utils.visualize_depth do to
  * rendered images ---------------------------------------------------------------------------------------------------------------------

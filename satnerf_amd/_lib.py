@@ -135,7 +135,8 @@ SIGNATURES = {
     "sr_blender_colors_scratch": (_i, [_i, _i, _i, _i, C.POINTER(_i64)]),
     "sr_blender_colors": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp]),
     "sr_pinhole_rays": (_i, [_i, _i, _f, _f, _f, _f, C.POINTER(_f), _f, _f, _vp, _vp]),
-    "sr_nearest_fill_scratch": (_i, [_i, _i, C.POINTER(_i64)]),
+    "sr_blender_perturb": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp]),
+    "sr_nearest_fill_scratch":(_i, [_i, _i, C.POINTER(_i64)]),
     "sr_nearest_fill": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "sr_colorize_scratch": (_i, [_i, C.POINTER(_i64)]),
     "sr_colorize": (_i, [_vp, _i, _i, _i64, _i64, _i, _i, _f, _f, _f, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),

@@ -14,6 +14,12 @@
 // The bounds of an output index are recomputed in the kernel from (n_in, n_out) in fp64 -- products, sums and a truncation, which IEEE
 // arithmetic gives identically on the host and the device -- so no bounds table exists that could point outside the source.
 //
+// sr_blender_perturb: add_perturbation (datasets/blender.py:61-79) on the decoded bytes, in front of sr_blender_colors: a per-band byte
+// table ("color": every band is a function of its own byte, built in fp64 on the host) and up to 16 filled rectangles ("occ").  One
+// launch, 8 bytes of traffic per pixel; the table and the rectangles travel by value in the kernel arguments, so nothing is uploaded
+// and nothing waits.  The table is staged in LDS as 256 packed dwords (one ds_read_b32 per band, each keeping its own byte); the
+// rectangles are read at a uniform index, i.e. through the scalar cache.
+//
 // sr_pinhole_rays: get_ray_directions + get_rays + the near / far columns; fp64 per pixel from the fp32 inputs, one rounding per
 // direction component, 32 contiguous bytes stored per lane.
 //
@@ -156,6 +162,62 @@ __global__ void __launch_bounds__(kLanes* kRows) convert_kernel(Source src, int 
 
 inline dim3 grid_for(int n_rows, int n_cols) { return dim3(blocks_for(n_cols, kLanes), blocks_for(n_rows, kRows)); }
 
+constexpr int kMaxRects = 16;
+constexpr int kPerturbRows = 16;  // rows of one workgroup of perturb_kernel: kRows lanes-rows, 4 pixels each
+
+// Everything perturb_kernel needs besides the image, by value in the kernel arguments (1.4 KB of the 4 KB a launch may carry)
+struct Perturb {
+  uint32_t lut[256];  // entry v: byte k = what band k's byte v becomes
+  int32_t rects[kMaxRects][4];  // x0, y0, x1, y1, inclusive
+  uint32_t fills[kMaxRects];    // packed, R in the low byte
+  int n_rects, has_lut;
+};
+
+template <bool PACKED>
+__device__ __forceinline__ void store_pixel(uint8_t* p, int64_t chan_stride, uint32_t u) {
+  if (PACKED) {
+    *reinterpret_cast<uint32_t*>(p) = u;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) p[k * chan_stride] = (uint8_t)(u >> (8 * k));
+}
+
+// One pass: read a pixel, look its four bytes up, test the rectangles in order (the last that holds the pixel wins), write it.  A
+// workgroup is 64 columns x 16 rows, four rows per lane, so the table is staged once per 1,024 pixels.  A pixel is read and written
+// by the same lane and by no other, so dst may be src.
+template <bool PACKED>
+__global__ void __launch_bounds__(kLanes* kRows) perturb_kernel(Source src, uint8_t* __restrict__ dst, int n_rows, int n_cols, Perturb p) {
+  __shared__ uint32_t lut[256];
+  if (p.has_lut) {  // uniform over the launch
+    const int t = threadIdx.y * kLanes + threadIdx.x;
+    lut[t] = p.lut[t];
+    __syncthreads();
+  }
+  const int c = blockIdx.x * kLanes + threadIdx.x;
+  if (c >= n_cols) return;
+  constexpr int kPer = kPerturbRows / kRows;
+  const int r0 = __builtin_amdgcn_readfirstlane(blockIdx.y * kPerturbRows + threadIdx.y);  // this lane's rows: r0 + j kRows
+  uint32_t u[kPer] = {};
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)  // all four loads in flight before the first use
+    if (r0 + j * kRows < n_rows) u[j] = load_pixel<PACKED>(src, r0 + j * kRows, c);
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int r = r0 + j * kRows;
+    if (r >= n_rows) return;
+    uint32_t v = u[j];
+    if (p.has_lut)
+      v = (lut[v & 255u] & 0xffu) | (lut[(v >> 8) & 255u] & 0xff00u) | (lut[(v >> 16) & 255u] & 0xff0000u) | (lut[v >> 24] & 0xff000000u);
+    for (int k = 0; k < p.n_rects; ++k) {  // one 16-byte scalar load per rectangle, no branch on its outcome
+      const int32_t* q = p.rects[k];
+      const bool inside = (c >= q[0]) & (r >= q[1]) & (c <= q[2]) & (r <= q[3]);
+      v = inside ? p.fills[k] : v;
+    }
+    store_pixel<PACKED>(dst + r * src.row_stride + c * src.pix_stride, src.chan_stride, v);
+  }
+}
+
 struct Pinhole {
   float fx, fy, cx, cy, m[12], near, far;
 };
@@ -261,6 +323,38 @@ extern "C" int sr_blender_colors(const uint8_t* src, int src_h, int src_w, int64
     hipLaunchKernelGGL((resample_kernel<true, false>), grid_for(out_h, out_w), block, 0, s, from, a, out_h, out_w, 1, 1, mid, out);
   }
   return check_launch("blender resample_kernel (vertical)");
+}
+
+extern "C" int sr_blender_perturb(const uint8_t* src, uint8_t* dst, int h, int w, int64_t row_stride, int64_t pix_stride, int64_t chan_stride,
+                                  const uint8_t* lut, const int32_t* rects, const uint8_t* fills, int n_rects, void* stream) {
+  SR_REQUIRE(src && dst, "sr_blender_perturb: null image (src %p, dst %p)", (const void*)src, (const void*)dst);
+  SR_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "sr_blender_perturb: the sides must lie in 1..%d (got %d x %d)", kMaxSide, h, w);
+  constexpr int64_t kMaxStride = 1ll << 40;  // keeps the extent below free of overflow
+  SR_REQUIRE(row_stride >= 1 && pix_stride >= 1 && chan_stride >= 1 && row_stride <= kMaxStride && pix_stride <= kMaxStride && chan_stride <= kMaxStride,
+             "sr_blender_perturb: strides must be positive byte counts up to 2^40 (got row %lld, pixel %lld, channel %lld)",
+             (long long)row_stride, (long long)pix_stride, (long long)chan_stride);
+  SR_REQUIRE(n_rects >= 0 && n_rects <= kMaxRects, "sr_blender_perturb: n_rects must lie in 0..%d (got %d)", kMaxRects, n_rects);
+  SR_REQUIRE(n_rects == 0 || (rects && fills), "sr_blender_perturb: null rects or fills with n_rects = %d", n_rects);
+  const int64_t extent = (h - 1) * row_stride + (w - 1) * pix_stride + 3 * chan_stride + 1;  // bytes from the first to past the last
+  const uintptr_t a = reinterpret_cast<uintptr_t>(src), b = reinterpret_cast<uintptr_t>(dst);
+  SR_REQUIRE(a == b || (a < b ? b - a : a - b) >= (uintptr_t)extent,
+             "sr_blender_perturb: dst must be src itself or not overlap it (the image spans %lld bytes)", (long long)extent);
+  Perturb p{};
+  p.n_rects = n_rects, p.has_lut = lut != nullptr;
+  if (lut)
+    for (int v = 0; v < 256; ++v) p.lut[v] = (uint32_t)lut[v] | ((uint32_t)lut[256 + v] << 8) | ((uint32_t)lut[512 + v] << 16) | ((uint32_t)lut[768 + v] << 24);
+  for (int k = 0; k < n_rects; ++k) {
+    for (int j = 0; j < 4; ++j) p.rects[k][j] = rects[4 * k + j];
+    p.fills[k] = (uint32_t)fills[4 * k] | ((uint32_t)fills[4 * k + 1] << 8) | ((uint32_t)fills[4 * k + 2] << 16) | ((uint32_t)fills[4 * k + 3] << 24);
+  }
+  const Source from{src, row_stride, pix_stride, chan_stride};
+  const bool packed = pix_stride == 4 && chan_stride == 1 && (row_stride & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) == 0;
+  const dim3 grid(blocks_for(w, kLanes), blocks_for(h, kPerturbRows)), block(kLanes, kRows);
+  if (packed)
+    hipLaunchKernelGGL(perturb_kernel<true>, grid, block, 0, (hipStream_t)stream, from, dst, h, w, p);
+  else
+    hipLaunchKernelGGL(perturb_kernel<false>, grid, block, 0, (hipStream_t)stream, from, dst, h, w, p);
+  return check_launch("blender perturb_kernel");
 }
 
 extern "C" int sr_pinhole_rays(int h, int w, float fx, float fy, float cx, float cy, const float* c2w, float near, float far, float* out,

@@ -399,8 +399,10 @@ def load_rays(root_dir, split="train", img_downscale=1.0, device="cuda", cache_d
     return out
 
 
-def _colors_on_device(op, what, image, h, w, device, out, layout):
-    """``ops.<op>`` of a uint8 image (array or tensor, host or device) uploaded to ``device``, with that device current."""
+def _colors_on_device(op, what, image, h, w, device, out, layout, perturb=None):
+    """``ops.<op>`` of a uint8 image (array or tensor, host or device) uploaded to ``device``, with that device current.  ``perturb``:
+    (lut, rects, fills) for ``ops.blender_perturb`` to apply to the uploaded bytes first -- in place when the upload made a copy, into
+    a new tensor when the bytes are still the caller's."""
     import contextlib
 
     import numpy as np
@@ -412,7 +414,11 @@ def _colors_on_device(op, what, image, h, w, device, out, layout):
         raise ValueError(f"image must be uint8 ({what}), got {t.dtype}")
     dev = torch.device(device)
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-        return getattr(ops, op)(t.to(dev).contiguous(), int(h), int(w), out=out, layout=layout)
+        u = t.to(dev).contiguous()
+        if perturb is not None and any(p is not None for p in perturb):
+            lut, rects, fills = perturb
+            u = ops.blender_perturb(u, lut, rects, fills, layout=layout, out=u if u is not t else None)
+        return getattr(ops, op)(u, int(h), int(w), out=out, layout=layout)
 
 
 def colors_from_image(image, h, w, device="cuda", out=None, layout=None):
@@ -501,13 +507,49 @@ def load_dataset(root_dir, img_dir, split="train", img_downscale=1.0, device="cu
     return rays
 
 
-def blender_colors_from_image(image, h, w, device="cuda", out=None, layout=None):
+def blender_perturbation(seed, perturbation):
+    """The host-side parameters of ``add_perturbation(img, perturbation, seed)`` (datasets/blender.py:61-79) for one frame: (lut, rects,
+    fills), ready for ``ops.blender_perturb``.
+
+    ``"color"``: s = uniform(0.8, 1.2, 3), b = uniform(-0.2, 0.2, 3), and a colour band's byte v becomes
+    ``uint8(255 * clip(s * (v / 255.0) + b, 0, 1))`` in fp64 -- a function of the byte alone, so ``lut`` (4, 256) uint8 holds it exactly;
+    the alpha row is ``uint8(255 * (v / 255.0))``, the identity.  ``"occ"``: left, top = randint(200, 400) twice, and rectangle i of ten
+    spans columns left + 20 i .. left + 20 (i + 1) and rows top .. top + 200, both ends included, filled with
+    ``choice(range(256), 3)`` of the generator seeded 10 * seed + i and alpha 255: ``rects`` (10, 4) int32 [x0, y0, x1, y1] and
+    ``fills`` (10, 4) uint8.  A part that ``perturbation`` does not name is None.  Both parts reseed with ``seed``, as the reference
+    does.  Unlike the reference, which seeds numpy's global generator, the draws come from ``np.random.RandomState`` objects (the same
+    streams), and the process's global generator is left alone.  ``perturbation`` must be a subset of {"color", "occ"}."""
+    import numpy as np
+
+    if isinstance(perturbation, str) or not set(perturbation).issubset({"color", "occ"}):
+        raise ValueError(f'Only "color" and "occ" perturbations are supported! (got {perturbation!r})')
+    seed = int(seed)
+    lut = rects = fills = None
+    if "color" in perturbation:
+        g = np.random.RandomState(seed)
+        s, b = g.uniform(0.8, 1.2, size=3), g.uniform(-0.2, 0.2, size=3)
+        x = np.repeat((np.arange(256) / 255.0)[:, None], 4, 1)
+        x[:, :3] = np.clip(s * x[:, :3] + b, 0, 1)
+        lut = np.ascontiguousarray((255 * x).astype(np.uint8).T)
+    if "occ" in perturbation:
+        g = np.random.RandomState(seed)
+        left, top = g.randint(200, 400), g.randint(200, 400)
+        rects, fills = np.empty((10, 4), np.int32), np.full((10, 4), 255, np.uint8)
+        for i in range(10):
+            rects[i] = left + 20 * i, top, left + 20 * (i + 1), top + 200
+            fills[i, :3] = np.random.RandomState(10 * seed + i).choice(range(256), 3)
+    return lut, rects, fills
+
+
+def blender_colors_from_image(image, h, w, device="cuda", out=None, layout=None, perturb=None):
     """((h * w, 3) fp32 colours, (h * w,) bool valid_mask) of one 8-bit RGBA image on the GPU, as ``BlenderDataset`` makes them
     (datasets/blender.py:136-139,179-183): Pillow's Lanczos resize to h x w byte for byte, ``u8 / 255``, the blend onto white and
     ``alpha > 0``.  ``image``: a uint8 array or tensor, (H, W, 4) or (4, H, W), on the host or already on the
     device; the host uploads its 4 bytes per pixel and ``ops.blender_colors`` does the rest.  ``out``: (h * w, 3) fp32 rows on ``device``
-    to write the colours into; ``layout``: "hwc" / "chw" for an image whose shape reads both ways."""
-    return _colors_on_device("blender_colors", "8-bit RGBA", image, h, w, device, out, layout)
+    to write the colours into; ``layout``: "hwc" / "chw" for an image whose shape reads both ways.  ``perturb``: the (lut, rects, fills)
+    of ``blender_perturbation``; the uploaded bytes then go through ``ops.blender_perturb`` before the resize, as the reference perturbs
+    the full-size image (an image that was already on the device is left as it was)."""
+    return _colors_on_device("blender_colors", "8-bit RGBA", image, h, w, device, out, layout, perturb)
 
 
 def blender_rays(h, w, focal, c2w, near=2.0, far=6.0, device="cuda", out=None):
@@ -539,6 +581,25 @@ def load_blender(root_dir, split="train", img_wh=(400, 400), device="cuda", read
     alpha); so does an ``img_wh`` that is not square (the reference's assert).  The layout is read off the shape: exactly one of the
     first and last axes must be 4, so a 4 x W x 4 array is refused as ambiguous; an array whose first axis is 4 is taken as (4, H, W)
     whatever its last axis (a (4, W, 3) array cannot be told from an RGBA image three pixels wide)."""
+    return _load_blender(root_dir, (), split, img_wh, device, reader)
+
+
+def load_blender_perturbed(root_dir, perturbation, split="train", img_wh=(400, 400), device="cuda", reader=None):
+    """What ``BlenderDataset(root_dir, split, img_wh, perturbation)`` holds (datasets/blender.py:61-79,91-95,132-134,176-178,198-207), on
+    the GPU: NeRF-W's "images in the wild" variant of a Blender scene.  ``perturbation``: a subset of {"color", "occ"}; empty, this is
+    ``load_blender``, whose arguments, checks and return values it shares.
+
+    ``"train"``: frame t != 0 is perturbed with seed t -- ``blender_perturbation(t, perturbation)`` applied by ``ops.blender_perturb`` to
+    the full-size bytes, colour first, then the occluders, before the resize.  ``"test_train"``: frame idx != 0 is perturbed with seed
+    idx, and with a non-empty ``perturbation`` every dict (frame 0's too) also carries ``"original_rgbs"`` and
+    ``"original_valid_mask"`` of the unperturbed image.  ``"val"`` and ``"test"`` are never perturbed.  The draws do not touch numpy's
+    global generator (``blender_perturbation``)."""
+    blender_perturbation(0, perturbation)  # refuses an unknown name before anything is read
+    return _load_blender(root_dir, tuple(perturbation), split, img_wh, device, reader)
+
+
+def _load_blender(root_dir, perturbation, split, img_wh, device, reader):
+    """``load_blender_perturbed``; ``load_blender`` is its ``perturbation=()``."""
     import json
     import math
     import os
@@ -556,8 +617,9 @@ def load_blender(root_dir, split="train", img_wh=(400, 400), device="cuda", read
     dev = torch.device(device)
     read = _read_image_pillow if reader is None else reader
 
-    def block(frame, rays, rgbs):
-        """One frame's rays and colours into ``rays`` and ``rgbs``; returns (c2w, valid_mask)."""
+    def block(frame, rays, rgbs, seed=0, original=False):
+        """One frame's rays and colours into ``rays`` and ``rgbs``, perturbed with ``seed`` unless that is 0; returns (c2w, valid_mask),
+        and with ``original`` also the unperturbed image's (rgbs, valid_mask)."""
         c2w = np.array(frame["transform_matrix"], dtype=np.float64)[:3, :4].astype(np.float32)
         path = os.path.join(root_dir, frame["file_path"] + ".png")
         img = np.asarray(read(path))
@@ -570,8 +632,11 @@ def load_blender(root_dir, split="train", img_wh=(400, 400), device="cuda", read
             raise ValueError(f"{path} has shape {tuple(img.shape)}, which reads as (H, W, 4) and as (4, H, W): the loader cannot tell its "
                              "four bands from a side of four pixels")
         layout = "chw" if first else "hwc"
-        _, mask = blender_colors_from_image(img, h, w, dev, out=rgbs, layout=layout)
+        perturb = blender_perturbation(seed, perturbation) if seed and perturbation else None
+        _, mask = blender_colors_from_image(img, h, w, dev, out=rgbs, layout=layout, perturb=perturb)
         blender_rays(h, w, focal, c2w, near, far, dev, out=rays)
+        if original:
+            return c2w, mask, blender_colors_from_image(img, h, w, dev, layout=layout) if perturb else (rgbs.clone(), mask.clone())
         return c2w, mask
 
     frames = meta["frames"]
@@ -580,17 +645,20 @@ def load_blender(root_dir, split="train", img_wh=(400, 400), device="cuda", read
         all_rays = torch.empty(len(frames) * n, 8, dtype=torch.float32, device=dev)
         all_rgbs = torch.empty(len(frames) * n, 3, dtype=torch.float32, device=dev)
         for t, frame in enumerate(frames):
-            block(frame, all_rays[t * n:(t + 1) * n], all_rgbs[t * n:(t + 1) * n])
+            block(frame, all_rays[t * n:(t + 1) * n], all_rgbs[t * n:(t + 1) * n], seed=t)
         all_ts = torch.arange(len(frames), dtype=torch.int64, device=dev).repeat_interleave(n)
         return all_rays, all_rgbs, all_ts
     out = []
     for idx, frame in enumerate(frames[:8] if split == "val" else frames):
         rays = torch.empty(n, 8, dtype=torch.float32, device=dev)
         rgbs = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        c2w, mask = block(frame, rays, rgbs)
         t = idx if split == "test_train" and idx != 0 else 0
+        extras = split == "test_train" and bool(perturbation)
+        c2w, mask, *orig = block(frame, rays, rgbs, seed=t, original=extras)
         out.append({"rays": rays, "ts": torch.full((n,), t, dtype=torch.int64, device=dev), "rgbs": rgbs,
                     "c2w": torch.from_numpy(c2w).to(dev), "valid_mask": mask})
+        if extras:
+            out[-1]["original_rgbs"], out[-1]["original_valid_mask"] = orig[0]
     return out
 
 

@@ -1229,6 +1229,46 @@ def blender_colors(image_u8, out_h, out_w, out=None, layout=None, want_rgba=Fals
     return (out, mask, rgba) if want_rgba else (out, mask)
 
 
+def blender_perturb(image_u8, lut=None, rects=None, fills=None, layout=None, out=None):
+    """sr_blender_perturb: the reference's ``add_perturbation`` (datasets/blender.py:61-79) of one 8-bit RGBA image on the device, from
+    host-side parameters (``data.blender_perturbation`` draws them).  ``image_u8``: a contiguous uint8 device tensor, (H, W, 4) or
+    (4, H, W), the layout resolved as ``blender_colors`` resolves it.  ``lut``: (4, 256) uint8 on the host, band k's byte v becomes
+    ``lut[k, v]``; ``rects``: (n, 4) integers [x0, y0, x1, y1], both corners included, anywhere (clipped to the image), n <= 16, with
+    ``fills`` (n, 4) uint8 RGBA, applied in order after the table, so a later rectangle wins.  Either part may be None.  ``out``: a
+    tensor like ``image_u8`` to write into -- ``image_u8`` itself works in place -- or None for a new one; it is returned.  The
+    parameters travel in the kernel's arguments: nothing is uploaded and nothing waits."""
+    import numpy as np
+
+    h, w, strides = _image_u8(image_u8, 4, layout)
+    if out is None:
+        out = torch.empty_like(image_u8)
+    elif out is not image_u8:
+        out = _chk(out, "out", torch.uint8)
+        if out.shape != image_u8.shape or out.device != image_u8.device:
+            raise ValueError(f"out must be {tuple(image_u8.shape)} on {image_u8.device}, got {tuple(out.shape)} on {out.device}")
+    if lut is not None:
+        lut = np.ascontiguousarray(lut.cpu().numpy() if torch.is_tensor(lut) else lut)
+        if lut.dtype != np.uint8 or lut.shape != (4, 256):
+            raise ValueError(f"lut must be (4, 256) uint8, got {lut.shape} {lut.dtype}")
+    if (rects is None) != (fills is None):
+        raise ValueError("rects and fills come together")
+    n = 0
+    if rects is not None:
+        rects, fills = np.asarray(rects), np.asarray(fills)
+        n = rects.shape[0]
+        if rects.ndim != 2 or rects.shape[1] != 4 or rects.dtype.kind not in "iu" or n > 16:
+            raise ValueError(f"rects must be (n, 4) integers with n <= 16, got {rects.shape} {rects.dtype}")
+        if fills.shape != (n, 4) or fills.dtype != np.uint8:
+            raise ValueError(f"fills must be ({n}, 4) uint8, got {fills.shape} {fills.dtype}")
+        if n and (rects.min() < -2 ** 31 or rects.max() >= 2 ** 31):
+            raise ValueError("rects must fit 32-bit integers")
+        rects, fills = np.ascontiguousarray(rects, dtype=np.int32), np.ascontiguousarray(fills)
+    host = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    _lib.call("sr_blender_perturb", _p(image_u8), _p(out), h, w, strides[0], strides[1], strides[2], host(lut), host(rects), host(fills), n,
+              _stream())
+    return out
+
+
 def pinhole_rays(h, w, fx, fy, cx, cy, c2w, near, far, out=None):
     """sr_pinhole_rays: the (h * w, 8) fp32 rows [o, d, near, far] of a pinhole camera, get_ray_directions + get_rays of the reference
     (datasets/blender.py:12-59): pixel (r, c) looks along ((c - cx) / fx, -(r - cy) / fy, -1) rotated by c2w[:, :3] and normalised, from

@@ -10,6 +10,11 @@ procedurally generated 800 x 800 RGBA image resized to 400 x 400, the reference'
   reference path    what the reference does on the host after the PNG decode (datasets/blender.py:136-139), restated: Pillow's
                     resize(LANCZOS), the bytes scaled to fp32 [0, 1], the blend onto white in torch on the CPU, and the upload of the
                     (h*w, 3) rows (host clock over 5 calls; torch's CPU threads as configured)
+  perturb ...       sr_blender_perturb on the 800 x 800 frame in place, the bytes already on the device (HIP events, as above): the colour
+                    table alone, the ten occluders alone, both (seed 3: the strip lies inside, 40,401 pixels)
+  blender_colors_from_image perturbed  the same as blender_colors_from_image with perturb = both: one more launch on the uploaded bytes
+  reference perturbation  add_perturbation (datasets/blender.py:61-79) on the host, restated with the draws made beforehand: numpy's
+                    fp64 scale, clip and cast of the whole frame, then Pillow's ten rectangles (host clock over 5 calls)
   reference rays    its rays (:51-59,142-149), restated: fp32 torch on the CPU rotates and normalises precomputed camera-frame
                     directions, attaches origin, near and far, and uploads the rows (host clock over 50 calls)
 Usage: bench_blender.py"""
@@ -72,6 +77,19 @@ def host_colors(pil_img):
     return (rows[:, :3] * alpha + (1 - alpha)).to(dev)
 
 
+def host_perturbation(pil_img, s, b, rects, fills):
+    """The host's way to the perturbed frame: numpy scales, clips and casts in fp64, Pillow draws the rectangles."""
+    from PIL import Image, ImageDraw
+
+    x = np.array(pil_img) / 255.0
+    x[..., :3] = np.clip(s * x[..., :3] + b, 0, 1)
+    img = Image.fromarray((255 * x).astype(np.uint8))
+    draw = ImageDraw.Draw(img)
+    for (x0, y0, x1, y1), fill in zip(rects, fills):
+        draw.rectangle(((x0, y0), (x1, y1)), fill=tuple(fill[:3]))
+    return img
+
+
 def host_rays(cam_dirs, pose):
     """The host's way to the same rows in fp32 torch: rotate the camera-frame directions, normalise, attach origin, near and far."""
     rot, origin = pose[:, :3], pose[:, 3]
@@ -107,10 +125,23 @@ def main():
     def pinhole():
         _lib.call("sr_pinhole_rays", OUT, OUT, focal, focal, OUT / 2, OUT / 2, c2w_c, 2.0, 6.0, ops._p(rays), ops._stream())
 
+    lut, rects, fills = data.blender_perturbation(3, ["color", "occ"])
+    frame = on_dev.clone()  # perturbed in place over and over: the time does not depend on the bytes
+
+    def perturb(lut, rects, fills):
+        _lib.call("sr_blender_perturb", ops._p(frame), ops._p(frame), SRC, SRC, 4 * SRC, 4, 1, None if lut is None else lut.ctypes.data,
+                  None if rects is None else rects.ctypes.data, None if rects is None else fills.ctypes.data, 0 if rects is None else len(rects),
+                  ops._stream())
+
     legs = {
         "horizontal pass": lambda: event_ms(lambda: colors(1)),
         "both passes": lambda: event_ms(lambda: colors(0)),
         "pinhole rays": lambda: event_ms(pinhole),
+        "perturb colour": lambda: event_ms(lambda: perturb(lut, None, None)),
+        "perturb occluders": lambda: event_ms(lambda: perturb(None, rects, fills)),
+        "perturb both": lambda: event_ms(lambda: perturb(lut, rects, fills)),
+        "blender_colors_from_image perturbed": lambda: host_ms(
+            lambda: data.blender_colors_from_image(img, OUT, OUT, device=dev, out=rgbs, perturb=(lut, rects, fills)), HOST_REPS["fast"]),
         "blender_colors_from_image": lambda: host_ms(lambda: data.blender_colors_from_image(img, OUT, OUT, device=dev, out=rgbs), HOST_REPS["fast"]),
         "blender_rays": lambda: host_ms(lambda: data.blender_rays(OUT, OUT, focal, c2w, device=dev, out=rays), HOST_REPS["fast"]),
     }
@@ -119,6 +150,9 @@ def main():
 
         pil_img = Image.fromarray(img, "RGBA")
         legs["reference path"] = lambda: host_ms(lambda: host_colors(pil_img), HOST_REPS["slow"])
+        g = np.random.RandomState(3)
+        s, b = g.uniform(0.8, 1.2, size=3), g.uniform(-0.2, 0.2, size=3)
+        legs["reference perturbation"] = lambda: host_ms(lambda: host_perturbation(pil_img, s, b, rects.tolist(), fills.tolist()), HOST_REPS["slow"])
     except ImportError:
         print("Pillow is not installed: the reference's colour path is not timed")
     legs["reference rays"] = lambda: host_ms(lambda: host_rays(directions, c2w_t), HOST_REPS["fast"])
@@ -137,6 +171,10 @@ def main():
         theirs = host_colors(pil_img)
         ours, _ = data.blender_colors_from_image(img, OUT, OUT, device=dev)
         print(f"  colours equal to the reference path bit for bit: {torch.equal(ours, theirs)}", flush=True)
+        theirs = torch.from_numpy(np.asarray(host_perturbation(pil_img, s, b, rects.tolist(), fills.tolist())).copy())
+        ours = ops.blender_perturb(on_dev, lut, rects, fills).cpu()
+        print(f"  perturbed bytes equal to the reference perturbation: {torch.equal(ours, theirs)} "
+              f"({SRC} x {SRC}: {8 * SRC * SRC / 1e6:.2f} MB read and written per launch)", flush=True)
     print(f"  max |rays - reference rays| = {(data.blender_rays(OUT, OUT, focal, c2w, device=dev) - host_rays(directions, c2w_t)).abs().max().item():.2e}",
           flush=True)
 
