@@ -322,6 +322,50 @@ int sr_grad_tail_adam(const float* partial, const int32_t* gidx, const float* gs
                       float grad_scale, const sr_pack_scatter* pack, void* stream);
 int sr_adam_step_graph(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                        float beta2, float eps, float grad_scale, float* state, int zero_grad, void* stream);
+
+/* ---- fixed-order sky and embedding gradients (deterministic training steps) ---------------------------------------------------------
+ * sr_sky_bwd, sr_embedding_bwd and the two tail launches add per-block / per-ray sums into g_* with float atomics: the order the sums land
+ * in, and so the last bits of these gradients, depend on scheduling.  The *_det twins below store the SAME sums into caller-provided scratch
+ * and let the last block to arrive add them up in a fixed order -- fp32 adds only, no FMA:
+ *   sky parameter i:            acc = 0.0f; for b = 0 .. n_sky_blocks-1: acc += sky_part[b][i];                        g[i] += acc
+ *   embedding element (row, c): acc = 0.0f; for r = 0 .. n_rays-1, increasing, where ts[r] == row: acc += emb_part[r][c];  g_emb[row][c] += acc
+ * Rows of g_emb that no ray names are not touched.  The arrival is the one the HIP memory model asks for (workgroup barrier, one thread's
+ * agent-scope acq_rel fetch_add, barrier); the last arriver resets the counter.
+ * Scratch, in 4-byte words (the library owns no memory: the caller allocates it 16-byte aligned, zeroes word 0 ONCE and may reuse the buffer
+ * for every launch; launches sharing a scratch must be ordered, e.g. on one stream):
+ *   [0]      arrival counter (uint32; zero between launches), [1..3] padding to 16 bytes
+ *   sky_part n_sky_blocks = ceil(n_rays / 32) rows of 7 * hidden + 3 floats; row b = the sums of rays [32 b, 32 b + 32) in the order of the
+ *            head's parameters: g_w1 (hidden x 3, row-major) | g_b1 (hidden) | g_w2 (3 x hidden, row-major) | g_b2 (3)
+ *   emb_part n_rays x tau floats: emb_part[r][c] = sum_j d_t[r][j][c]
+ *   first    n_rays uint32: 1 where no earlier ray of the batch names ray r's row (where the reduction starts that row's chain), else 0
+ * sr_late_grad_scratch_bytes (host only) = 4 * (4 + n_sky_blocks * (7 * hidden + 3) + n_rays * tau + n_rays); -1 for n_rays < 0, hidden < 1
+ * or tau < 1.  Every word behind the counter is rewritten by each launch.
+ * sr_sky_bwd_det / sr_embedding_bwd_det replace sr_sky_bwd / sr_embedding_bwd (same arguments, plus the scratch and its size in bytes).  A
+ * stand-alone launch has only its own part: sr_sky_bwd_det reads the scratch as [counter | sky_part], sr_embedding_bwd_det as [counter |
+ * emb_part | first]; a buffer of sr_late_grad_scratch_bytes is large enough for either.
+ * sr_grad_tail_det replaces sr_grad_tail: the same three block ranges, the sky and embedding ranges storing partials; the last of THEIR blocks
+ * to arrive (counter: scratch word 0) reduces in order into g_*.  The split-K range is sr_grad_tail's.
+ * sr_grad_tail_adam_det replaces sr_grad_tail_adam: the last arriver (counter: state[3], as sr_grad_tail_adam; scratch word 0 is not used)
+ * reduces in order and then updates the `late_idx` parameters from the reduced gradients; the split-K / Adam / re-pack range is
+ * sr_grad_tail_adam's.  Results repeat bit for bit per box and per switch setting (sr_wgrad_plan depends on the CU count). */
+int64_t sr_late_grad_scratch_bytes(int64_t n_rays, int hidden, int tau);
+int sr_sky_bwd_det(const float* sun, int sun_stride, int64_t n, int hidden, const float* w1, const float* b1, const float* w2,
+                   const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* scratch,
+                   int64_t scratch_bytes, void* stream);
+int sr_embedding_bwd_det(const float* d_t, const int64_t* ts, int64_t n_rays, int n_samples, int tau, float* g_emb, float* scratch,
+                         int64_t scratch_bytes, void* stream);
+int sr_grad_tail_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
+                     float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden,
+                     const float* w1, const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1,
+                     float* g_w2, float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* scratch,
+                     int64_t scratch_bytes, void* stream);
+int sr_grad_tail_adam_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
+                          float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
+                          const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
+                          float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params,
+                          float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1,
+                          float beta2, float eps, float grad_scale, const sr_pack_scatter* pack, float* scratch, int64_t scratch_bytes,
+                          void* stream);
 /* sr_adam_step_graph that also re-packs (r06: the data-parallel step = the single-GPU step + one collective): Adam on all n elements of
  * the flat buffers, and each of the first n_packed parameters (the coarse model's; `pack->map` holds n_packed x 2 words) written into its
  * places of the weight streams as sr_grad_tail_adam does.  Sequence at N > 1: ... sr_grad_tail | all-reduce of `grads` | sr_adam_step_pack

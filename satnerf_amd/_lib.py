@@ -94,6 +94,14 @@ SIGNATURES = {
     "sr_grad_tail_adam": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
                                _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
     "sr_adam_step_graph": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _vp, _i, _vp]),
+    # the fixed-order twins: their atomic twin's arguments, then (scratch, scratch_bytes) in front of the stream
+    "sr_late_grad_scratch_bytes": (_i64, [_i64, _i, _i]),
+    "sr_sky_bwd_det": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sr_embedding_bwd_det": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp]),
+    "sr_grad_tail_det": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                              _vp, _vp, _i64, _vp]),
+    "sr_grad_tail_adam_det": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                   _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _vp, _i64, _vp]),
     "sr_adam_step_pack": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _vp, _i, _i64, _vp, _vp]),
     "sr_pack_all": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sr_gather_scale_f32": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),

@@ -416,6 +416,15 @@ __global__ void __launch_bounds__(256) gather_scale_kernel(const float* __restri
 // Block = 32 rays; thread (k = hidden unit, half) reduces 16 rays in registers, the two halves meet in LDS, then one atomicAdd
 // per parameter per block (1024 rays -> 32 blocks x 899 atomics).
 constexpr int kSkyRays = 32;
+// The body computes a block's sums; the emitter says where they go.  kStore = false: float atomics into g_* (they land in order of arrival).
+// kStore = true (the *_det launches below): plain stores, g_* then being the four parts of the block's row of the caller's scratch -- 7 * hidden + 3
+// floats in the order of the head's parameters [w1 (hidden x 3) | b1 (hidden) | w2 (3 x hidden) | b2 (3)], each written by every launch.
+template <bool kStore>
+__device__ __forceinline__ void late_emit(float* dst, float v) {
+  if constexpr (kStore) *dst = v;
+  else atomicAdd(dst, v);
+}
+template <bool kStore = false>
 __device__ __forceinline__ void sky_bwd_body(int block, const float* __restrict__ sun, int sun_stride, long n, int hidden,
                                              const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
                                              const float* __restrict__ sky, const float* __restrict__ d_sky, float* __restrict__ g_w1,
@@ -458,15 +467,15 @@ __device__ __forceinline__ void sky_bwd_body(int block, const float* __restrict_
     if (half == 0 && k < hidden) {
 #pragma unroll
       for (int c = 0; c < 7; ++c) a[c] += comb[kk][c];
-      atomicAdd(&g_w1[k * 3], a[0]), atomicAdd(&g_w1[k * 3 + 1], a[1]), atomicAdd(&g_w1[k * 3 + 2], a[2]), atomicAdd(&g_b1[k], a[3]);
-      atomicAdd(&g_w2[k], a[4]), atomicAdd(&g_w2[hidden + k], a[5]), atomicAdd(&g_w2[2 * hidden + k], a[6]);
+      late_emit<kStore>(&g_w1[k * 3], a[0]), late_emit<kStore>(&g_w1[k * 3 + 1], a[1]), late_emit<kStore>(&g_w1[k * 3 + 2], a[2]), late_emit<kStore>(&g_b1[k], a[3]);
+      late_emit<kStore>(&g_w2[k], a[4]), late_emit<kStore>(&g_w2[hidden + k], a[5]), late_emit<kStore>(&g_w2[2 * hidden + k], a[6]);
     }
     __syncthreads();
   }
   if (threadIdx.x < 3) {
     float acc = 0.f;
     for (int i = 0; i < nr; ++i) acc += ray[i][3 + threadIdx.x];
-    atomicAdd(&g_b2[threadIdx.x], acc);
+    late_emit<kStore>(&g_b2[threadIdx.x], acc);
   }
 }
 
@@ -479,24 +488,27 @@ __global__ void __launch_bounds__(256) sky_bwd_kernel(const float* __restrict__ 
 }
 
 // ---- embedding gradient (nn.Embedding backward, rendering.py:100): d_emb[ts[r]] += sum_j d_t[r, j, :] ----------------------
+// kStore as above: the ray's sum over its samples is added atomically to its row of g_emb, or stored as g_emb[ray][component], g_emb then being
+// the emb_part of the caller's scratch.
+template <bool kStore = false>
 __device__ __forceinline__ void embedding_bwd_body(int block, const float* __restrict__ d_t, const long long* __restrict__ ts, long n_rays,
                                                    int S, int tau, float* __restrict__ g_emb) {
   const int lane = threadIdx.x & 63;
   const long r = (long)block * kRaysPerBlock + (threadIdx.x >> 6);
   if (r >= n_rays) return;
-  const long row = ts[r];
+  const long row = kStore ? r : ts[r];
   const float* src = d_t + r * (long)S * tau;  // the ray's S x tau block is contiguous
   if (64 % tau == 0) {  // lane k always meets component k % tau: coalesced sweep, then reduce lanes of equal k % tau
     float a = 0.f;
     for (int k = lane; k < S * tau; k += 64) a += src[k];
     for (int m = 32; m >= tau; m >>= 1) a += __shfl_xor(a, m, 64);
-    if (lane < tau) atomicAdd(&g_emb[row * tau + lane], a);
+    if (lane < tau) late_emit<kStore>(&g_emb[row * tau + lane], a);
   } else {
     for (int i = 0; i < tau; ++i) {
       float a = 0.f;
       for (int j = lane; j < S; j += 64) a += src[j * tau + i];
       a = wave_sum(a);
-      if (lane == 0) atomicAdd(&g_emb[row * tau + i], a);
+      if (lane == 0) late_emit<kStore>(&g_emb[row * tau + i], a);
     }
   }
 }
@@ -504,6 +516,107 @@ __device__ __forceinline__ void embedding_bwd_body(int block, const float* __res
 __global__ void __launch_bounds__(256) embedding_bwd_kernel(const float* __restrict__ d_t, const long long* __restrict__ ts, long n_rays,
                                                            int S, int tau, float* __restrict__ g_emb) {
   embedding_bwd_body(blockIdx.x, d_t, ts, n_rays, S, tau, g_emb);
+}
+
+// ---- fixed-order late gradients (the *_det launches) ---------------------------------------------------------------------------------------
+// The float atomics above land in the order their blocks happen to run: two runs of the same step differ in the last bits of the sky head's
+// and the embedding rows' gradients.  The *_det launches run the same bodies with the storing emitters and let ONE block -- the last to
+// arrive -- add the stored sums up in a fixed order (fp32 adds only, no FMA):
+//   sky parameter i:         acc = 0; for b = 0 .. n_sky_blocks-1: acc += sky_part[b][i];               g[i] += acc
+//   embedding element (w,c): acc = 0; for r = 0 .. n_rays-1 with ts[r] == w: acc += emb_part[r][c];    g_emb[w][c] += acc
+// Rows that no ray names are not touched.  Scratch (caller's memory, sr_late_grad_scratch_bytes): [arrival counter, padded to 16 bytes |
+// sky_part (ceil(n_rays / 32) rows of 7 * hidden + 3) | emb_part (n_rays x tau) | first (n_rays words: 1 = no earlier ray names this ray's row)].
+struct LateScratch {
+  unsigned* arrive; float* sky_part; float* emb_part; unsigned* first;
+};
+constexpr long kLateHeadFloats = 4;  // the counter word, padded to 16 bytes
+__host__ __device__ inline long sky_row_floats(int hidden) { return 7L * hidden + 3; }
+// (n_sky / n_emb: the rays of the sky and of the embedding part -- the batch's for a tail, 0 for the part a stand-alone launch does not have)
+inline long late_scratch_floats(long n_sky, int hidden, long n_emb, int tau) {
+  return kLateHeadFloats + (n_sky + kSkyRays - 1) / kSkyRays * sky_row_floats(hidden) + n_emb * tau + n_emb;
+}
+inline LateScratch late_scratch(float* scratch, long n_sky, int hidden, long n_emb, int tau) {
+  LateScratch d;
+  d.arrive = reinterpret_cast<unsigned*>(scratch);
+  d.sky_part = scratch + kLateHeadFloats;
+  d.emb_part = d.sky_part + (n_sky + kSkyRays - 1) / kSkyRays * sky_row_floats(hidden);
+  d.first = reinterpret_cast<unsigned*>(d.emb_part + n_emb * tau);
+  return d;
+}
+
+// (embedding blocks of a *_det launch) whether ray r is the first of the batch to name its row: the wave compares the r entries before its own.
+// Every wave does this beside its sum, so that the block that reduces knows where each row's chain starts without a pass of its own over ts.
+__device__ __forceinline__ void emb_first_of_row(int block, const long long* __restrict__ ts, long n_rays, unsigned* first) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)block * kRaysPerBlock + (threadIdx.x >> 6);
+  if (r >= n_rays) return;
+  const long long row = ts[r];
+  bool seen = false;
+  for (long j = lane; j < r; j += 64) seen |= ts[j] == row;
+  const bool any = __ballot(seen) != 0ull;
+  if (lane == 0) first[r] = any ? 0u : 1u;
+}
+
+// The model-conforming arrival (the SR_TAIL_RELEASE == 1 branch of grad_tail_adam_kernel): after the workgroup barrier ONE thread arrives with an
+// agent-scope acq_rel fetch_add -- release: the barrier makes the block's stores happen-before it; acquire: the last arriver then reads what the
+// earlier ones released -- and the barrier behind it carries that to the block's other threads.  The partials are plain stores that live in an
+// XCD's L2 until released: the relaxed arrive of the product tail, which rests on float atomics being performed at the memory side, is NOT enough here.
+__device__ __forceinline__ bool arrive_last(unsigned* counter, int n_arrivals) {
+  __shared__ int last;
+  __syncthreads();
+  if (threadIdx.x == 0) last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(n_arrivals - 1);
+  __syncthreads();
+  return last != 0;
+}
+
+// (one block, 256 threads) the ordered sums of the comment above.  A thread owns a sky parameter, or one (first ray of a row, component) pair and
+// then walks ts from that ray on: every element is one thread's sequential chain of adds, whatever the block's scheduling.
+__device__ __forceinline__ void sky_reduce(const float* part, int n_sky_blocks, int hidden, float* g_w1, float* g_b1, float* g_w2, float* g_b2) {
+#pragma clang fp contract(off)
+  const int row = (int)sky_row_floats(hidden);
+  for (int i = threadIdx.x; i < row; i += 256) {
+    float acc = 0.f;
+    for (int b = 0; b < n_sky_blocks; ++b) acc += part[(long)b * row + i];
+    float* g = i < 3 * hidden ? g_w1 + i : i < 4 * hidden ? g_b1 + (i - 3 * hidden) : i < 7 * hidden ? g_w2 + (i - 4 * hidden) : g_b2 + (i - 7 * hidden);
+    *g += acc;
+  }
+}
+__device__ __forceinline__ void emb_reduce(const float* part, const unsigned* first, const long long* ts, long n_rays, int tau, float* g_emb) {
+#pragma clang fp contract(off)
+  for (long it = threadIdx.x; it < n_rays * tau; it += 256) {
+    const long r = it / tau;
+    const int c = (int)(it - r * tau);
+    if (first[r] == 0u) continue;
+    const long long row = ts[r];
+    float acc = 0.f;
+#pragma unroll 8
+    for (long r2 = r; r2 < n_rays; ++r2) {  // (both loads unconditional: the unrolled loop keeps eight of each in flight)
+      const float v = part[r2 * tau + c];
+      acc = ts[r2] == row ? acc + v : acc;
+    }
+    g_emb[row * tau + c] += acc;
+  }
+}
+
+__global__ void __launch_bounds__(256) sky_bwd_det_kernel(const float* __restrict__ sun, int sun_stride, long n, int hidden,
+                                                         const float* __restrict__ w1, const float* __restrict__ b1,
+                                                         const float* __restrict__ w2, const float* __restrict__ sky,
+                                                         const float* __restrict__ d_sky, float* g_w1, float* g_b1, float* g_w2, float* g_b2,
+                                                         const LateScratch d) {
+  float* row = d.sky_part + (long)blockIdx.x * sky_row_floats(hidden);
+  sky_bwd_body<true>(blockIdx.x, sun, sun_stride, n, hidden, w1, b1, w2, sky, d_sky, row, row + 3 * hidden, row + 4 * hidden, row + 7 * hidden);
+  if (!arrive_last(d.arrive, gridDim.x)) return;
+  sky_reduce(d.sky_part, gridDim.x, hidden, g_w1, g_b1, g_w2, g_b2);
+  if (threadIdx.x == 0) __hip_atomic_store(d.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(256) embedding_bwd_det_kernel(const float* __restrict__ d_t, const long long* __restrict__ ts, long n_rays,
+                                                               int S, int tau, float* g_emb, const LateScratch d) {
+  embedding_bwd_body<true>(blockIdx.x, d_t, ts, n_rays, S, tau, d.emb_part);
+  emb_first_of_row(blockIdx.x, ts, n_rays, d.first);
+  if (!arrive_last(d.arrive, gridDim.x)) return;
+  emb_reduce(d.emb_part, d.first, ts, n_rays, tau, g_emb);
+  if (threadIdx.x == 0) __hip_atomic_store(d.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // gradient tail of the training fast path: [split-K reduction + scatter of the MLP weight gradients | sky-head gradients |
@@ -528,6 +641,36 @@ __device__ __forceinline__ float tail_sum(const float* __restrict__ partial, con
   const int2 t = b < kTailTab ? tab[b] : int2{blocks[kWgTableInts * b + kWgSlices], blocks[kWgTableInts * b + kWgFirstSlice]};
   return wg_sum_slices(partial, t.x, t.y, k - b * kWgBlockFloats);
 }
+// (a *_det tail) block b of the sky / embedding ranges stores its sums; the last of those blocks to arrive at `arrive` adds them up in order
+// into g_* and is told so.  The counter is left for the caller to reset: sr_grad_tail_adam_det's last block still has the update to do.
+__device__ __forceinline__ bool late_partials_and_reduce(const GradTailParams& q, const LateScratch& d, unsigned* arrive, int b) {
+  if (b < q.blocks_sky) {
+    float* row = d.sky_part + (long)b * sky_row_floats(q.hidden);
+    sky_bwd_body<true>(b, q.sun, q.sun_stride, q.n_rays, q.hidden, q.w1, q.b1, q.w2, q.sky, q.d_sky, row, row + 3 * q.hidden, row + 4 * q.hidden, row + 7 * q.hidden);
+  } else {
+    embedding_bwd_body<true>(b - q.blocks_sky, q.d_t, q.ts, q.n_rays, q.S, q.tau, d.emb_part);
+    emb_first_of_row(b - q.blocks_sky, q.ts, q.n_rays, d.first);
+  }
+  if (!arrive_last(arrive, q.blocks_sky + q.blocks_emb)) return false;
+  sky_reduce(d.sky_part, q.blocks_sky, q.hidden, q.g_w1, q.g_b1, q.g_w2, q.g_b2);
+  emb_reduce(d.emb_part, d.first, q.ts, q.n_rays, q.tau, q.g_emb);
+  return true;
+}
+
+// the split-K range of the two tail launches: block b of that range
+__device__ __forceinline__ void tail_split_k(const GradTailParams& q, int b) {
+  __shared__ int2 tab[kTailTab];
+  tail_table_to_lds(tab, q.blocks, q.n_blocks);
+  const long i = (long)b * 256 + threadIdx.x;
+  const bool in = i < q.n_params;
+  // everything that does not depend on the sum is requested before it
+  const int k = in ? q.gidx[i] : -1;
+  const float gs = in ? q.gscale[i] : 0.f;
+  const float g0 = in && q.accumulate ? q.grad[i] : 0.f;
+  __syncthreads();
+  if (k < 0) return;
+  q.grad[i] = g0 + tail_sum(q.partial, tab, q.blocks, k) * gs;
+}
 __global__ void __launch_bounds__(256) grad_tail_kernel(const GradTailParams q) {
   // the two small latency-bound ranges (atomics, one wave per ray) come FIRST in dispatch order so that they run under the cover
   // of the bandwidth-bound reduction instead of forming the kernel's tail
@@ -542,17 +685,16 @@ __global__ void __launch_bounds__(256) grad_tail_kernel(const GradTailParams q) 
     return;
   }
   b -= q.blocks_emb;
-  __shared__ int2 tab[kTailTab];
-  tail_table_to_lds(tab, q.blocks, q.n_blocks);
-  const long i = (long)b * 256 + threadIdx.x;
-  const bool in = i < q.n_params;
-  // everything that does not depend on the sum is requested before it
-  const int k = in ? q.gidx[i] : -1;
-  const float gs = in ? q.gscale[i] : 0.f;
-  const float g0 = in && q.accumulate ? q.grad[i] : 0.f;
-  __syncthreads();
-  if (k < 0) return;
-  q.grad[i] = g0 + tail_sum(q.partial, tab, q.blocks, k) * gs;
+  tail_split_k(q, b);
+}
+// sr_grad_tail_det: the sky and embedding ranges store partials and their last block reduces them in order; the split-K range is the same code
+__global__ void __launch_bounds__(256) grad_tail_det_kernel(const GradTailParams q, const LateScratch d) {
+  const int b = blockIdx.x, n_late_blocks = q.blocks_sky + q.blocks_emb;
+  if (b >= n_late_blocks) {
+    tail_split_k(q, b - n_late_blocks);
+    return;
+  }
+  if (late_partials_and_reduce(q, d, d.arrive, b) && threadIdx.x == 0) __hip_atomic_store(d.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- gradient tail + Adam in ONE launch (single-GPU captured step) -------------------------------------------------------------------
@@ -593,6 +735,27 @@ __device__ __forceinline__ void pack_scatter_words(const sr_pack_scatter& k, int
     k.hi[pos] = (uint16_t)h;
     if (k.lo) k.lo[pos] = (uint16_t)l;
   }
+}
+// the split-K / Adam / pack-scatter range of the two tail + Adam launches: block b of that range (tab, step_size, sqrt_bc2: the launch's prologue)
+__device__ __forceinline__ void tail_adam_split_k(const TailAdamParams& a, const int2* tab, int b, float step_size, float sqrt_bc2) {
+  const GradTailParams& q = a.q;
+  const long i = (long)b * 256 + threadIdx.x;
+  const bool in = i < q.n_params;
+  // everything that does not depend on the split-K sum is requested before it: the launch used to be a chain of five dependent memory
+  // round trips per thread (gidx -> table row -> 10 slices -> 8 slices -> optimizer state), 74 % of its wave cycles parked (r05 PMC)
+  const int k = in ? q.gidx[i] : -1;  // (< 0: no weight-gradient GEMM produces it: on the `late` list)
+  const bool live = k >= 0;
+  const float gs = in ? q.gscale[i] : 0.f;
+  const float g0 = in && q.accumulate ? q.grad[i] : 0.f;  // what the solar-correction / depth-supervision passes of this step left
+  float p = in ? a.p[i] : 0.f, m = in ? a.m[i] : 0.f, v = in ? a.v[i] : 0.f;
+  int2 w = int2{-1, -1};
+  if (a.pack.map != nullptr && in) w = reinterpret_cast<const int2*>(a.pack.map)[i];
+  if (!live) return;
+  float g = g0 + tail_sum(q.partial, tab, q.blocks, k) * gs;
+  adam_one(p, g, m, v, step_size, a.b1, a.b2, a.eps, a.grad_scale, sqrt_bc2, 1);
+  a.p[i] = p, a.m[i] = m, a.v[i] = v;
+  q.grad[i] = 0.f;
+  if (a.pack.map != nullptr) pack_scatter_words(a.pack, w, p);
 }
 __global__ void __launch_bounds__(256) grad_tail_adam_kernel(const TailAdamParams a) {
   const GradTailParams& q = a.q;
@@ -651,24 +814,37 @@ __global__ void __launch_bounds__(256) grad_tail_adam_kernel(const TailAdamParam
     if (threadIdx.x == 0) __hip_atomic_store(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
-  b -= n_atomic;
-  const long i = (long)b * 256 + threadIdx.x;
-  const bool in = i < q.n_params;
-  // everything that does not depend on the split-K sum is requested before it: the launch used to be a chain of five dependent memory
-  // round trips per thread (gidx -> table row -> 10 slices -> 8 slices -> optimizer state), 74 % of its wave cycles parked (r05 PMC)
-  const int k = in ? q.gidx[i] : -1;  // (< 0: no weight-gradient GEMM produces it: on the `late` list)
-  const bool live = k >= 0;
-  const float gs = in ? q.gscale[i] : 0.f;
-  const float g0 = in && q.accumulate ? q.grad[i] : 0.f;  // what the solar-correction / depth-supervision passes of this step left
-  float p = in ? a.p[i] : 0.f, m = in ? a.m[i] : 0.f, v = in ? a.v[i] : 0.f;
-  int2 w = int2{-1, -1};
-  if (a.pack.map != nullptr && in) w = reinterpret_cast<const int2*>(a.pack.map)[i];
-  if (!live) return;
-  float g = g0 + tail_sum(q.partial, tab, q.blocks, k) * gs;
-  adam_one(p, g, m, v, step_size, a.b1, a.b2, a.eps, a.grad_scale, sqrt_bc2, 1);
-  a.p[i] = p, a.m[i] = m, a.v[i] = v;
-  q.grad[i] = 0.f;
-  if (a.pack.map != nullptr) pack_scatter_words(a.pack, w, p);
+  tail_adam_split_k(a, tab, b - n_atomic, step_size, sqrt_bc2);
+}
+
+// sr_grad_tail_adam_det: the sky and embedding ranges store partials, their last block reduces them in order (late_partials_and_reduce, behind the
+// model-conforming arrive at the same counter) and then runs the `late` loop on the reduced gradients; the split-K range is the same code
+__global__ void __launch_bounds__(256) grad_tail_adam_det_kernel(const TailAdamParams a, const LateScratch d) {
+  const GradTailParams& q = a.q;
+  __shared__ float bc[2];
+  __shared__ int2 tab[kTailTab];
+  if (threadIdx.x == 0) {
+    const float t = a.state[0];
+    bc[0] = 1.0f - powf(a.b1, t), bc[1] = 1.0f - powf(a.b2, t);
+  }
+  tail_table_to_lds(tab, q.blocks, q.n_blocks);
+  __syncthreads();
+  const float lr = a.lr < 0.f ? a.state[1] : a.lr;
+  const float step_size = lr / bc[0], sqrt_bc2 = sqrtf(bc[1]);
+  const int b = blockIdx.x, n_late_blocks = q.blocks_sky + q.blocks_emb;
+  if (b >= n_late_blocks) {
+    tail_adam_split_k(a, tab, b - n_late_blocks, step_size, sqrt_bc2);
+    return;
+  }
+  if (!late_partials_and_reduce(q, d, a.arrive, b)) return;
+  __syncthreads();  // the loop below reads gradients that other threads of this block have just written (plain loads: same CU, same L1)
+  for (int k = threadIdx.x; k < a.n_late; k += 256) {
+    const int i = a.late[k];
+    float g = q.grad[i];
+    adam_one(a.p[i], g, a.m[i], a.v[i], step_size, a.b1, a.b2, a.eps, a.grad_scale, sqrt_bc2, 1);
+    q.grad[i] = 0.f;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- Adam + re-pack in ONE launch (data-parallel captured step, r06) ---------------------------------------------------------------------
@@ -867,15 +1043,41 @@ extern "C" int sr_sky_bwd(const float* sun, int sun_stride, int64_t n, int hidde
   return check_launch("sky_bwd_kernel");
 }
 
-extern "C" int sr_grad_tail(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                            float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
-                            const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                            float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, void* stream) {
+extern "C" int64_t sr_late_grad_scratch_bytes(int64_t n_rays, int hidden, int tau) {
+  if (n_rays < 0 || hidden < 1 || tau < 1) return -1;
+  return late_scratch_floats(n_rays, hidden, n_rays, tau) * (int64_t)sizeof(float);
+}
+
+// the scratch of a *_det launch: present, float-aligned and long enough for (n_rays, hidden, tau)
+static int late_scratch_checked(const char* who, float* scratch, int64_t scratch_bytes, int64_t n_sky, int hidden, int64_t n_emb, int tau, LateScratch* d) {
+  SR_REQUIRE(scratch != nullptr && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "%s: scratch must be a 16-byte aligned device pointer", who);
+  SR_REQUIRE((n_sky == 0 || hidden >= 1) && (n_emb == 0 || tau >= 1), "%s: hidden = %d, tau = %d", who, hidden, tau);
+  const int64_t need = late_scratch_floats(n_sky, hidden, n_emb, tau) * (int64_t)sizeof(float);
+  SR_REQUIRE(scratch_bytes >= need, "%s: scratch holds %lld bytes, %lld rays (hidden %d, tau %d) need %lld (sr_late_grad_scratch_bytes)", who,
+             (long long)scratch_bytes, (long long)(n_sky > n_emb ? n_sky : n_emb), hidden, tau, (long long)need);
+  *d = late_scratch(scratch, n_sky, hidden, n_emb, tau);
+  return 0;
+}
+
+extern "C" int sr_sky_bwd_det(const float* sun, int sun_stride, int64_t n, int hidden, const float* w1, const float* b1, const float* w2,
+                              const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* scratch,
+                              int64_t scratch_bytes, void* stream) {
+  SR_REQUIRE(sun && w1 && b1 && w2 && sky && d_sky && g_w1 && g_b1 && g_w2 && g_b2, "sr_sky_bwd_det: null pointer");
+  if (n <= 0) return 0;
+  LateScratch d;
+  if (late_scratch_checked("sr_sky_bwd_det", scratch, scratch_bytes, n, hidden, 0, 0, &d)) return 1;
+  hipLaunchKernelGGL(sky_bwd_det_kernel, dim3((unsigned)((n + kSkyRays - 1) / kSkyRays)), dim3(256), 0, (hipStream_t)stream, sun, sun_stride, (long)n, hidden,
+                     w1, b1, w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d);
+  return check_launch("sky_bwd_det_kernel");
+}
+
+static int grad_tail_fill(const char* who, GradTailParams& q, const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params,
+                          const int32_t* blocks, int n_blocks, float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden,
+                          const float* w1, const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
+                          float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb) {
   SR_REQUIRE(partial && gidx && gscale && blocks && grad && sun && w1 && b1 && w2 && sky && d_sky && g_w1 && g_b1 && g_w2 && g_b2 && d_t && ts && g_emb,
-             "sr_grad_tail: null pointer");
-  SR_REQUIRE(n_blocks >= 1, "sr_grad_tail: n_blocks = %d", n_blocks);
-  if (n_rays <= 0) return 0;
-  GradTailParams q;
+             "%s: null pointer", who);
+  SR_REQUIRE(n_blocks >= 1, "%s: n_blocks = %d", who, n_blocks);
   q.partial = partial, q.gidx = gidx, q.gscale = gscale, q.n_params = n_params, q.blocks = blocks, q.grad = grad;
   q.accumulate = accumulate, q.sun = sun, q.sun_stride = sun_stride, q.n_rays = n_rays, q.hidden = hidden, q.w1 = w1, q.b1 = b1, q.w2 = w2;
   q.sky = sky, q.d_sky = d_sky, q.g_w1 = g_w1, q.g_b1 = g_b1, q.g_w2 = g_w2, q.g_b2 = g_b2, q.d_t = d_t, q.ts = (const long long*)ts;
@@ -883,8 +1085,49 @@ extern "C" int sr_grad_tail(const float* partial, const int32_t* gidx, const flo
   q.blocks_unpack = (int)((n_params + 255) / 256);
   q.blocks_sky = (int)((n_rays + kSkyRays - 1) / kSkyRays);
   q.blocks_emb = (int)((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
+  return 0;
+}
+
+extern "C" int sr_grad_tail(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
+                            float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
+                            const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
+                            float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, void* stream) {
+  GradTailParams q;
+  if (grad_tail_fill("sr_grad_tail", q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1, b1, w2,
+                     sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
+    return 1;
+  if (n_rays <= 0) return 0;
   hipLaunchKernelGGL(grad_tail_kernel, dim3(q.blocks_unpack + q.blocks_sky + q.blocks_emb), dim3(256), 0, (hipStream_t)stream, q);
   return check_launch("grad_tail_kernel");
+}
+
+extern "C" int sr_grad_tail_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
+                                float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
+                                const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
+                                float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* scratch,
+                                int64_t scratch_bytes, void* stream) {
+  GradTailParams q;
+  if (grad_tail_fill("sr_grad_tail_det", q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1, b1,
+                     w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
+    return 1;
+  if (n_rays <= 0) return 0;
+  LateScratch d;
+  if (late_scratch_checked("sr_grad_tail_det", scratch, scratch_bytes, n_rays, hidden, n_rays, tau, &d)) return 1;
+  hipLaunchKernelGGL(grad_tail_det_kernel, dim3(q.blocks_unpack + q.blocks_sky + q.blocks_emb), dim3(256), 0, (hipStream_t)stream, q, d);
+  return check_launch("grad_tail_det_kernel");
+}
+
+static int tail_adam_fill(const char* who, TailAdamParams& a, float* params, float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late,
+                          float* state, float lr, float beta1, float beta2, float eps, float grad_scale, const sr_pack_scatter* pack) {
+  a.p = params, a.m = exp_avg, a.v = exp_avg_sq, a.late = late_idx, a.n_late = n_late, a.state = state;
+  a.arrive = reinterpret_cast<unsigned*>(state + 3);  // the schedule block's arrival counter (ray_device.h tick_when_all_read: unused by training steps)
+  a.lr = lr, a.b1 = beta1, a.b2 = beta2, a.eps = eps, a.grad_scale = grad_scale;
+  a.pack = sr_pack_scatter{};
+  if (pack != nullptr && pack->map != nullptr) {
+    SR_REQUIRE(pack->hi && pack->l0 && pack->n_f16 >= 0, "%s: pack needs the stream and the fc_net.0 table", who);
+    a.pack = *pack;
+  }
+  return 0;
 }
 
 extern "C" int sr_grad_tail_adam(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
@@ -893,30 +1136,35 @@ extern "C" int sr_grad_tail_adam(const float* partial, const int32_t* gidx, cons
                                  float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params,
                                  float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1,
                                  float beta2, float eps, float grad_scale, const sr_pack_scatter* pack, void* stream) {
-  SR_REQUIRE(partial && gidx && gscale && blocks && grad && sun && w1 && b1 && w2 && sky && d_sky && g_w1 && g_b1 && g_w2 && g_b2 && d_t && ts && g_emb,
-             "sr_grad_tail_adam: null pointer");
-  SR_REQUIRE(n_blocks >= 1, "sr_grad_tail_adam: n_blocks = %d", n_blocks);
+  TailAdamParams a;
+  if (grad_tail_fill("sr_grad_tail_adam", a.q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1, b1,
+                     w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
+    return 1;
   SR_REQUIRE(params && exp_avg && exp_avg_sq && state && (late_idx || n_late == 0) && n_late >= 0, "sr_grad_tail_adam: null optimizer pointer");
   if (n_rays <= 0) return 0;
-  TailAdamParams a;
-  GradTailParams& q = a.q;
-  q.partial = partial, q.gidx = gidx, q.gscale = gscale, q.n_params = n_params, q.blocks = blocks, q.grad = grad;
-  q.accumulate = accumulate, q.sun = sun, q.sun_stride = sun_stride, q.n_rays = n_rays, q.hidden = hidden, q.w1 = w1, q.b1 = b1, q.w2 = w2;
-  q.sky = sky, q.d_sky = d_sky, q.g_w1 = g_w1, q.g_b1 = g_b1, q.g_w2 = g_w2, q.g_b2 = g_b2, q.d_t = d_t, q.ts = (const long long*)ts;
-  q.S = n_samples, q.tau = tau, q.g_emb = g_emb, q.n_blocks = n_blocks;
-  q.blocks_unpack = (int)((n_params + 255) / 256);
-  q.blocks_sky = (int)((n_rays + kSkyRays - 1) / kSkyRays);
-  q.blocks_emb = (int)((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
-  a.p = params, a.m = exp_avg, a.v = exp_avg_sq, a.late = late_idx, a.n_late = n_late, a.state = state;
-  a.arrive = reinterpret_cast<unsigned*>(state + 3);  // the schedule block's arrival counter (ray_device.h tick_when_all_read: unused by training steps)
-  a.lr = lr, a.b1 = beta1, a.b2 = beta2, a.eps = eps, a.grad_scale = grad_scale;
-  a.pack = sr_pack_scatter{};
-  if (pack != nullptr && pack->map != nullptr) {
-    SR_REQUIRE(pack->hi && pack->l0 && pack->n_f16 >= 0, "sr_grad_tail_adam: pack needs the stream and the fc_net.0 table");
-    a.pack = *pack;
-  }
-  hipLaunchKernelGGL(grad_tail_adam_kernel, dim3(q.blocks_unpack + q.blocks_sky + q.blocks_emb), dim3(256), 0, (hipStream_t)stream, a);
+  if (tail_adam_fill("sr_grad_tail_adam", a, params, exp_avg, exp_avg_sq, late_idx, n_late, state, lr, beta1, beta2, eps, grad_scale, pack)) return 1;
+  hipLaunchKernelGGL(grad_tail_adam_kernel, dim3(a.q.blocks_unpack + a.q.blocks_sky + a.q.blocks_emb), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("grad_tail_adam_kernel");
+}
+
+extern "C" int sr_grad_tail_adam_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
+                                     float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
+                                     const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
+                                     float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params,
+                                     float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1,
+                                     float beta2, float eps, float grad_scale, const sr_pack_scatter* pack, float* scratch, int64_t scratch_bytes,
+                                     void* stream) {
+  TailAdamParams a;
+  if (grad_tail_fill("sr_grad_tail_adam_det", a.q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1,
+                     b1, w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
+    return 1;
+  SR_REQUIRE(params && exp_avg && exp_avg_sq && state && (late_idx || n_late == 0) && n_late >= 0, "sr_grad_tail_adam_det: null optimizer pointer");
+  if (n_rays <= 0) return 0;
+  if (tail_adam_fill("sr_grad_tail_adam_det", a, params, exp_avg, exp_avg_sq, late_idx, n_late, state, lr, beta1, beta2, eps, grad_scale, pack)) return 1;
+  LateScratch d;
+  if (late_scratch_checked("sr_grad_tail_adam_det", scratch, scratch_bytes, n_rays, hidden, n_rays, tau, &d)) return 1;
+  hipLaunchKernelGGL(grad_tail_adam_det_kernel, dim3(a.q.blocks_unpack + a.q.blocks_sky + a.q.blocks_emb), dim3(256), 0, (hipStream_t)stream, a, d);
+  return check_launch("grad_tail_adam_det_kernel");
 }
 
 extern "C" int sr_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
@@ -942,4 +1190,15 @@ extern "C" int sr_embedding_bwd(const float* d_t, const int64_t* ts, int64_t n_r
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)((n_rays + kRaysPerBlock - 1) / kRaysPerBlock)), dim3(256), 0, (hipStream_t)stream,
                      d_t, (const long long*)ts, (long)n_rays, n_samples, tau, g_emb);
   return check_launch("embedding_bwd_kernel");
+}
+
+extern "C" int sr_embedding_bwd_det(const float* d_t, const int64_t* ts, int64_t n_rays, int n_samples, int tau, float* g_emb, float* scratch,
+                                    int64_t scratch_bytes, void* stream) {
+  SR_REQUIRE(d_t && ts && g_emb, "sr_embedding_bwd_det: null pointer");
+  if (n_rays <= 0) return 0;
+  LateScratch d;
+  if (late_scratch_checked("sr_embedding_bwd_det", scratch, scratch_bytes, 0, 0, n_rays, tau, &d)) return 1;
+  hipLaunchKernelGGL(embedding_bwd_det_kernel, dim3((unsigned)((n_rays + kRaysPerBlock - 1) / kRaysPerBlock)), dim3(256), 0, (hipStream_t)stream,
+                     d_t, (const long long*)ts, (long)n_rays, n_samples, tau, g_emb, d);
+  return check_launch("embedding_bwd_det_kernel");
 }

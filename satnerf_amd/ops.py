@@ -788,6 +788,69 @@ def grad_tail_adam(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_
               float(eps), float(grad_scale), C.byref(ps) if ps is not None else None, _stream())
 
 
+# ---- fixed-order sky and embedding gradients (include/satrender.h: the *_det entry points) ---------------------------------------------
+def late_grad_scratch_bytes(n_rays, hidden, tau):
+    """Size in bytes of the scratch of the ``*_det`` launches (sr_late_grad_scratch_bytes, host only)."""
+    n = int(_lib.lib().sr_late_grad_scratch_bytes(int(n_rays), int(hidden), int(tau)))
+    if n < 0:
+        raise ValueError(f"late_grad_scratch_bytes: n_rays={n_rays}, hidden={hidden}, tau={tau}")
+    return n
+
+
+def late_grad_scratch(n_rays, hidden, tau, device):
+    """The scratch of the ``*_det`` launches for batches of up to ``n_rays`` rays: a zeroed float32 buffer (word 0 is the arrival counter, which
+    every launch leaves at zero) that may be reused for every step."""
+    return torch.zeros(late_grad_scratch_bytes(n_rays, hidden, tau) // 4, dtype=torch.float32, device=device)
+
+
+def _late_scratch(scratch, need=None):
+    """(pointer, size in bytes) of a ``*_det`` launch's scratch; ``need``: the bytes the launch asks for when the caller knows them (the
+    library checks in any case)."""
+    scratch = _chk(scratch, "scratch")
+    if need is not None and scratch.numel() * 4 < need:
+        raise ValueError(f"scratch holds {scratch.numel() * 4} bytes, the launch needs {need} (late_grad_scratch)")
+    return _p(scratch), scratch.numel() * 4
+
+
+def sky_bwd_det(sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, scratch):
+    """``sky_bwd`` with the per-block sums stored in ``scratch`` and added up in block order by the last block (sr_sky_bwd_det)."""
+    sun, stride = _rows(sun, "sun", 3)
+    _lib.call("sr_sky_bwd_det", _p(sun), stride, sun.shape[0], w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")), _p(_chk(d_sky, "d_sky")),
+              _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), *_late_scratch(scratch), _stream())
+
+
+def embedding_bwd_det(d_t, ts, n_rays, n_samples, tau, g_emb, scratch):
+    """``embedding_bwd`` with the per-ray sums stored in ``scratch`` and added up in ray order by the last block (sr_embedding_bwd_det)."""
+    _lib.call("sr_embedding_bwd_det", _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_rays, n_samples, tau, _p(_chk(g_emb, "g_emb")),
+              *_late_scratch(scratch), _stream())
+
+
+def grad_tail_det(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
+                  n_samples, tau, g_emb, scratch):
+    """``grad_tail`` whose sky and embedding gradients are summed in a fixed order (sr_grad_tail_det); ``scratch``: ``late_grad_scratch``."""
+    sun, stride = _rows(sun, "sun", 3)
+    _lib.call("sr_grad_tail_det", _p(partial), _p(_chk(gidx, "gidx", torch.int32)), _p(_chk(gscale, "gscale")), gidx.numel(), _p(plan), plan.shape[0],
+              _p(_chk(grad_flat, "grad_flat")), 1, _p(sun), stride, n_rays, w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")),
+              _p(_chk(d_sky, "d_sky")), _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_samples, tau,
+              _p(_chk(g_emb, "g_emb")), *_late_scratch(scratch, late_grad_scratch_bytes(n_rays, w1.shape[0], tau)), _stream())
+
+
+def grad_tail_adam_det(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays, n_samples,
+                       tau, g_emb, params, exp_avg, exp_avg_sq, late_idx, state, scratch, lr=-1.0, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,
+                       pack=None):
+    """``grad_tail_adam`` whose sky and embedding gradients are summed in a fixed order before the last block updates the ``late_idx``
+    parameters (sr_grad_tail_adam_det); ``scratch``: ``late_grad_scratch``.  The arrival counter is ``state[3]``, as in ``grad_tail_adam``."""
+    sun, stride = _rows(sun, "sun", 3)
+    ps = _pack_scatter_struct(pack, gidx.numel()) if pack is not None else None
+    _lib.call("sr_grad_tail_adam_det", _p(partial), _p(_chk(gidx, "gidx", torch.int32)), _p(_chk(gscale, "gscale")), gidx.numel(), _p(plan), plan.shape[0],
+              _p(_chk(grad_flat, "grad_flat")), 1, _p(sun), stride, n_rays, w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")),
+              _p(_chk(d_sky, "d_sky")), _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_samples, tau,
+              _p(_chk(g_emb, "g_emb")), _p(_chk(params, "params")), _p(_chk(exp_avg, "exp_avg")), _p(_chk(exp_avg_sq, "exp_avg_sq")),
+              _p(_chk(late_idx, "late_idx", torch.int32)), late_idx.numel(), _p(_chk(state, "state")), float(lr), float(betas[0]), float(betas[1]),
+              float(eps), float(grad_scale), C.byref(ps) if ps is not None else None,
+              *_late_scratch(scratch, late_grad_scratch_bytes(n_rays, w1.shape[0], tau)), _stream())
+
+
 def _pack_scatter_struct(pack, n_model):
     if pack["map"].shape != (n_model, 2):
         raise ValueError("pack map does not match the parameter count")

@@ -81,9 +81,11 @@ Launches = namedtuple("Launches", "fused_forward tick pack_first sampler graph_s
 
 
 def launches(*, collective, fmt, n_samples, render_fused_ok, kernel_rng=False, adam_in_graph=False, pack_in_tail=False, snerf=False, bank=False,
-             ray_bank=False, late_idx=True, env=os.environ):
+             ray_bank=False, late_idx=True, deterministic=False, env=os.environ):
     """The three state flags are ``Trainer``'s (a capture's ``CaptureState``, or what a caller assigned by hand; none before a capture);
-    ``bank``: the colour batch comes from a ray bank, ``ray_bank``: that bank is a ``RayBank`` (the forward launch can read its rows)."""
+    ``bank``: the colour batch comes from a ray bank, ``ray_bank``: that bank is a ``RayBank`` (the forward launch can read its rows);
+    ``deterministic`` (``Trainer(deterministic=True)``, not an environment switch): the tail launch is its fixed-order twin -- ``names``
+    carries sr_grad_tail_det / sr_grad_tail_adam_det, every other field is what it is without it."""
     fused = fused_forward(fmt, n_samples, render_fused_ok, env)
     ticking = bool(kernel_rng or adam_in_graph)
     # r05, single-GPU captured step: no sr_pack_all launch -- the launch that updates the parameters (sr_grad_tail_adam) also writes
@@ -116,7 +118,7 @@ def launches(*, collective, fmt, n_samples, render_fused_ok, kernel_rng=False, a
         names += ["sr_render_loss"] if n_samples <= 64 else ["sr_composite_fwd", "sr_satnerf_loss", "sr_composite_bwd"]
     # data parallel (r06): the N > 1 step is the N = 1 step split at the collective -- sr_grad_tail (the reduction) | all-reduce of the flat
     # gradient | sr_adam_step_pack (Adam + the re-pack of the weight streams): no sr_pack_all, no separate Adam launch
-    names += ["sr_satnerf_mlp_bwd", "sr_satnerf_wgrad8" if fmt == 8 else "sr_satnerf_wgrad", "sr_grad_tail_adam" if tail_adam else "sr_grad_tail"]
+    names += ["sr_satnerf_mlp_bwd", "sr_satnerf_wgrad8" if fmt == 8 else "sr_satnerf_wgrad", ("sr_grad_tail_adam" if tail_adam else "sr_grad_tail") + ("_det" if deterministic else "")]
     if not tail_adam:
         names += (["all_reduce"] if collective else []) + ["sr_adam_step" + {"adam_graph": "_graph", "adam_pack": "_pack", "adam_eager": ""}[update]]
     return Launches(fused, 2 if pit else 0, False if pit else "ticks" if ticking else "quiet", sampler, graph_sampler,

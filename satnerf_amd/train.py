@@ -175,13 +175,17 @@ class Trainer:
     """
 
     def __init__(self, models, args, world_size=1, lr=5e-4, loss_fn=None, use_graph=True, steps_per_epoch=None, lr_gamma=0.9,
-                 warmup_epochs=2, lr_steps_per_epoch=None):
+                 warmup_epochs=2, lr_steps_per_epoch=None, deterministic=False):
         """``steps_per_epoch`` (= len(dataset) // batch_size, train_utils.py:14-15) switches the reference's schedule on:
         StepLR(step_size=1, gamma=``lr_gamma``) per epoch (main.py:86-94, train_utils.py:41-57) and ``metrics.SNerfLoss`` instead
         of ``SatNerfLoss`` while epoch < ``warmup_epochs`` (main.py:128-131 hard-codes 2).  None = constant rate, SatNerfLoss
         from the first step.  ``lr_steps_per_epoch`` (default: ``steps_per_epoch``) is the number of batches after which Lightning
         steps the StepLR: a DataLoader epoch has ceil(len(dataset) / batch_size) batches (drop_last=False, main.py:96-110) while the
-        warm-up test divides by the floor -- pass both when the batch size does not divide the dataset."""
+        warm-up test divides by the floor -- pass both when the batch size does not divide the dataset.
+        ``deterministic=True``: two trainings from the same seed, data and box produce the same bits -- the tail launch sums the sky head's
+        and the embedding rows' gradients in a fixed order (sr_grad_tail_det / sr_grad_tail_adam_det) instead of by float atomics, the only
+        scheduling-dependent accumulation of the kernel-direct step.  It needs that step (default loss, no fine model, a fused-training
+        model with its embedding): the layer path's linear.hip gradients and a ``loss_fn``'s autograd are not covered -- ValueError."""
         self._snerf = args.model == "s-nerf"
         self._caller_args = args  # main.py:132 decays args.noise_std in place: the caller's object follows, also for s-nerf's private copy
         if args.model == "sat-nerf" and steps_per_epoch is None:
@@ -229,6 +233,14 @@ class Trainer:
             gidx = packing.backward_maps(models["coarse"].feat, models["coarse"].t_embedding_dims)["gidx"]
             late = np.concatenate([np.nonzero(gidx < 0)[0], np.arange(gidx.size, p.numel())])
             self._late_idx = torch.from_numpy(late.astype(np.int32)).to(p.device)
+        self.deterministic = bool(deterministic)
+        if self.deterministic and not (self.direct and self._late_idx is not None):
+            why = ("a loss_fn's autograd graph accumulates in an order of its own" if loss_fn is not None else
+                   "the parameters are not on the GPU" if not p.is_cuda else
+                   "this model set trains through render_rays + autograd and the layer path, whose linear.hip weight gradients are float atomics"
+                   if not self.direct else "the flat buffer is not [coarse model | embedding]: the tail launch has no list of late parameters")
+            raise ValueError(f"deterministic=True needs the kernel-direct training step: {why}")
+        self._late_scratch = {}  # (deterministic) scratch of the tail's ordered sums, allocated once per batch size
         self._graph, self._static, self._graph_banks = None, None, None
         self._pre_bufs, self._pack_in_tail, self._packed_version = None, False, None
         self.max_inflight = int(os.environ.get("SATNERF_MAX_INFLIGHT", "0"))
@@ -251,7 +263,16 @@ class Trainer:
         flags = dict(kernel_rng=self._kernel_rng, adam_in_graph=self._adam_in_graph, pack_in_tail=self._pack_in_tail) if captured else {}
         return step_plan.launches(collective=self._collective, fmt=_fmt_of(self.args), n_samples=self.args.n_samples, snerf=self._snerf,
                                   render_fused_ok=ops.render_fused_ok(self.models["coarse"].feat, _mode_of(self.args), self.args.n_samples),
-                                  bank=bank is not None, ray_bank=type(bank).__name__ == "RayBank", late_idx=self._late_idx is not None, **flags)
+                                  bank=bank is not None, ray_bank=type(bank).__name__ == "RayBank", late_idx=self._late_idx is not None,
+                                  deterministic=self.deterministic, **flags)
+
+    def _tail_scratch(self, n, hidden, tau, device):
+        """(deterministic) the scratch of the tail's ordered sums: one buffer per batch size, kept for the trainer's life -- a captured step
+        holds its address as one more static buffer."""
+        key = (n, hidden, tau)
+        if key not in self._late_scratch:
+            self._late_scratch[key] = ops.late_grad_scratch(n, hidden, tau, device)
+        return self._late_scratch[key]
 
     def _fused_forward(self):
         """True when the colour pass's forward is ONE launch (sr_satnerf_render_train), step_plan.fused_forward."""
@@ -323,14 +344,19 @@ class Trainer:
             loss = torch.cat([loss.view(-1), self._depth_pass(*depth, noise_std * 0.9).view(-1)])  # main.py:132 decays the noise first
         tail = (partial, wplan, maps["gidx"], maps["gscale"], model.flat_grads(), rays[:, 8:11], *sw[:3], sky, d_sky, sk[0].weight.grad,
                 sk[0].bias.grad, sk[2].weight.grad, sk[2].bias.grad, d_t, ts, n, s, tau, emb.weight.grad)
+        # deterministic: the plan names the tail's fixed-order twin (the sky head's and the embedding rows' sums stored in a scratch and added
+        # up in block / ray order by the last block instead of landing as float atomics); everything else of the step is the same
+        det = ("sr_grad_tail_adam_det" if plan.tail == "tail_adam" else "sr_grad_tail_det") in plan.names
+        scratch = (self._tail_scratch(n, sw[0].shape[0], tau, rays.device),) if det else ()
         if plan.tail == "tail_adam":
             # lr < 0: the kernel reads the current rate from sched[1], so a scheduler can change it under graph replay
-            ops.grad_tail_adam(*tail, self.state.params, self.exp_avg, self.exp_avg_sq, self._late_idx, self.adam_state, lr=-1.0,
-                               grad_scale=1.0 / self.world, pack=None if plan.pack_first else model.pack_scatter(mode))
+            (ops.grad_tail_adam_det if det else ops.grad_tail_adam)(*tail, self.state.params, self.exp_avg, self.exp_avg_sq, self._late_idx,
+                                                                    self.adam_state, *scratch, lr=-1.0, grad_scale=1.0 / self.world,
+                                                                    pack=None if plan.pack_first else model.pack_scatter(mode))
             return loss
         # data parallel (r06): the N > 1 step is the N = 1 step split at the collective -- sr_grad_tail (the reduction) | all-reduce of the flat
         # gradient | sr_adam_step_pack (Adam + the re-pack of the weight streams, `_update`): no sr_pack_all, no separate Adam launch
-        ops.grad_tail(*tail)
+        (ops.grad_tail_det if det else ops.grad_tail)(*tail, *scratch)
         if not plan.update_after_replay:  # the update rides in the same graph (the RCCL all-reduce captured with it, or SATNERF_TAIL_ADAM=0)
             self._update(plan.update)
         return loss
