@@ -1,40 +1,39 @@
 #!/usr/bin/env python3
-"""Generator of the hand-placed gfx950 instruction stream of the dX kernel's TRUNK (csrc/mlp_bwd.inc, 8-bit workspaces, width 256).
+"""Generator of the hand-placed gfx950 instruction stream of the dX kernel's TRUNK (csrc/mlp_bwd.inc, 8-bit workspaces, both widths).
 
 The seven transposed trunk layers bL7 .. bL1 are two thirds of the data-gradient kernel (896 of its 1,308 MFMAs per 32-point tile):
     d a_{l-1} = W_l^T d pre_l  (8 output tiles x 16 k-steps),      d pre_{l-1} = d a_{l-1} * cos(2 pi phase_{l-1}),
 d pre_{l-1} handed on in registers as bf16 B fragments and written to the dpre workspace as MX8 (codec8.h) for the weight-gradient kernel.
 = autograd's backward through fc_net.2 .. fc_net.14 of SatNeRF.forward (models/satnerf.py:156-180) for every sample point.
 
-Why now.  r03 tried this (tools/experiments/bwd_trunk_gen.py) and measured no gain: its epilogue -- cvt + scale + v_cos, multiply, pack,
-fma + cvt_pk_u8 per value: ~120 VALU per 16-MFMA tile -- costs ~556 cycles of VALU issue per tile against 512 matrix cycles, so two
-waves per SIMD were VALU-bound at ~70 cycles per MFMA however the stream was placed.  r04 shortened the codecs (one v_perm per phase
-byte, v_max3 tree, one-rounding MX8 encode in v_pk_fma_f32 + byte gathers: 84 VALU, ~470 cycles per tile), which moved the VALU time UNDER
-the matrix time -- but hipcc's schedule of that code (1,336 instructions per layer: 10.4 per MFMA, 26 SALU and 11 waits per tile, the
-epilogue of tile t - 1 in one lump after tile t's chain) gained 3 %.  With the epilogue spread over the MFMA gaps the two pipes overlap,
-as they do in the forward core (gen/fwd_core.py, whose recipe this is):
-  * MFMA i consumes piece i of the trunk's part of the transposed stream from a flat LDS ring of R pieces fed by LDS-DMA rows of 8 pieces
-    (one 1-KiB request per wave and row); a rendezvous (counted vmcnt + s_barrier) every GROUP tiles makes a group's pieces visible, after
-    which the rows whose ring slots every wave has consumed are requested;
-  * A fragments are read PF MFMAs ahead (ds_read_b128 into a ring of PF + 1 register quads, counted lgkmcnt before each MFMA);
-  * the tile's saved phases (one 16-byte load per lane) are fetched two tiles ahead straight into registers; loads retire in order, so
-    every vmcnt wait is an exact count of the LOADS (LDS-DMA rows and phase loads) issued after the one needed -- stores are left out of
-    the count (they may complete out of order: a wait can only get longer);
-  * the epilogue of tile t - 1 sits in the gaps of tile t's MFMAs, FILL instructions per gap, software-pipelined over value pairs so that
-    no instruction waits for the transcendental unit: perm perm cos cos | perm perm | pk_mul | cos cos | cvt_pk ...
+Why now.  r03 tried this (tools/experiments/bwd_trunk_gen.py, last held by commit a4fc281) and measured no gain: its epilogue -- cvt +
+scale + v_cos, multiply, pack, fma + cvt_pk_u8 per value: ~120 VALU per 16-MFMA tile -- costs ~556 cycles of VALU issue per tile against
+512 matrix cycles, so two waves per SIMD were VALU-bound at ~70 cycles per MFMA however the stream was placed.  r04 shortened the codecs
+(one v_perm per phase byte, v_max3 tree, one-rounding MX8 encode in v_pk_fma_f32 + byte gathers: 84 VALU, ~470 cycles per tile), which
+moved the VALU time UNDER the matrix time -- but hipcc's schedule of that code (1,336 instructions per layer: 10.4 per MFMA, 26 SALU and
+11 waits per tile, the epilogue of tile t - 1 in one lump after tile t's chain) gained 3 %.  With the epilogue spread over the MFMA gaps
+the two pipes overlap, as they do in the forward cores.
+
+The scheduler and the lane model are stream_common.py's (read that docstring first), shared with the three forward cores: ring, DMA
+rows, rendezvous, A-fragment prefetch, the tagged load queue, the epilogue queue, text and command line.  This file states what is
+particular to the trunk:
+  * one plane, no ragged row, no prologue rows; 8 waves (width 256: two per SIMD) or 4 (512: one per SIMD, Y and the A ring in AGPRs);
+  * the tile's saved phases (one 16-byte load per lane) are fetched two tiles ahead straight into registers (``gap_loads``); they sit in
+    the same in-order queue as the DMA rows, and the epilogue waits for them by tag;
+  * the epilogue of tile t - 1 sits in the gaps of tile t's MFMAs, FILL INSTRUCTIONS per gap, producers first so that no instruction
+    waits for the transcendental unit: 16 perm | 16 cos | 8 pk_mul | 8 cvt_pk | max tree | exponent | 8 pk_fma | byte gathers | store;
   * per layer: the eight MX8 exponent bytes of a lane go to the scale unit, and their maximum over the wave (SDWA byte maxima, six DPP
-    steps, one readlane) to the wave's cell of the exponent-maxima table (mlp_layout.h; the weight-gradient kernel's fp16 range fit).
+    steps, one readlane) to the wave's cell of the exponent-maxima table (mlp_layout.h; the weight-gradient kernel's fp16 range fit);
+  * at a layer boundary the whole queue is emptied, not only up to the operand's producers (``flush_producers``).
 The arithmetic per value is exactly mlp_bwd.inc's (bpack / mx8_exponent / mx8_encode): the workspace bytes are bit-identical to the
-compiler-scheduled kernel's, which tests/test_hip_backward.py asserts on the GPU; tests/test_bwd_core.py executes the stream on a
-lane-accurate CPU model.
+compiler-scheduled kernel's, which tests/test_hip_backward.py asserts on the GPU; tests/test_bwd_core.py executes the stream on
+``TrunkMachine`` (below), which also holds the hazards the assembler does not pad inside inline asm: trans -> VALU use (1 state), VALU
+write -> MFMA operand (2), MFMA D -> VALU read, M0 write -> LDS-DMA (1), VALU write -> DPP read (2), VALU write -> v_readlane (1).
 
-Hazards the assembler does not pad inside inline asm: trans -> VALU use (1 state: the pipelining above), VALU write -> MFMA operand (2),
-MFMA D -> VALU read (the epilogue starts two MFMAs after the tile's last), M0 write -> LDS-DMA (1), VALU write -> DPP read (2).
+``python bwd_core.py`` writes csrc/mlp_bwd{,512}_trunk_a{1,2}.inc and csrc/mlp_bwd{,512}_trunk_clobbers.inc.
 
-``python bwd_core.py`` writes csrc/mlp_bwd_trunk_a{1,2}.inc and csrc/mlp_bwd_trunk_clobbers.inc.
-
-Registers: v[0:63] X, v[64:127] Y (d pre vectors, ping-pong: X is the statement's in/out operand), v[128:159] two accumulators,
-v[160:183] A ring, v[184:199] phase ring (4 tiles), v[200:203] temporaries, v[204:211] two store quads, v[212:213] scale bytes,
+Registers (width 256): v[0:63] X, v[64:127] Y (d pre vectors, ping-pong: X is the statement's in/out operand), v[128:159] two accumulators,
+v[160:183] A ring, v[184:199] phase ring (4 tiles), v[204:211] two store quads, v[212:213] scale bytes,
 v214 max, v215 exponent, v[216:217] 2^(133-E) (low register used), v[218:219] the rounding constant, v220 = 0x43000000, v221 / v222 LDS
 read bases, v223 stream offset, v224 phase offset, v225 dpre offset, v[226:229] temporaries, v230 LDS address of the wave's maxima cells, v[232:247] the tile's sixteen cosines / rounded MX8 values.
 Scalar operands: %[sb] trunk part of the stream, %[wb] ring + wave * 1024, %[ab] activation workspace, %[db] dpre workspace, %[m0save].
@@ -44,8 +43,10 @@ from __future__ import annotations
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stream_common import A0, Ins, rn  # noqa: E402  (unified register numbering: the 512-wide kernel uses both files, one wave per SIMD)
+from stream_common import A0, LANE, CoreBase, LaneModel, Tile, bf16_bits, bf16_to_f32, frag_to_f32, main, rn  # noqa: E402,F401
 
 
 class Geo:
@@ -70,7 +71,6 @@ class Geo:
             self.ACC = (128, 144)
             self.AR0 = 160
             self.PH0 = 184
-            self.T0 = 200                            # (unused since the producers-first epilogue; kept out of the clobbers' way)
             self.SV = (204, 208)
             self.EB = 212
             self.M, self.E, self.INV, self.MAGIC, self.K43 = 214, 215, 216, 218, 220
@@ -105,83 +105,75 @@ class Geo:
 
 S_SEL = ("s84", "s85", "s86", "s87")     # v_perm selectors of phase byte k: the byte lands in bits 8..15 of 0x43000000 (codec8.h phase8_rev)
 S_B4A, S_B4B, S_MAX = "s88", "s89", "s90"  # bytes4() selectors (codec8.h), the wave maximum
+STEM = {256: "mlp_bwd_trunk", 512: "mlp_bwd512_trunk"}
 
 
-class Trunk:
-    def __init__(self, auxs, feat=256, PF=5, ablate=()):
-        self.g = g = Geo(feat)
-        self.auxs, self.R, self.PF, self.GROUP, self.FILL = auxs, g.R, PF, g.GROUP, g.FILL
-        assert self.R % g.NW == 0 and PF + 1 <= g.NA
-        self.ablate = set(ablate)   # timing experiments (results wrong): noepi, nodma, nophase, nostore
-        self.ins = []
-        self.vm = []           # outstanding vector-memory LOADS in issue order (tags)
-        self.p_unit = None     # unit POFF / SOFF currently point at
-        self.s_unit = None
-        self._build()
+class Trunk(CoreBase):
+    FEAT, SRC, SAVE, LABEL, WS, KEEP_FIRST = 256, ("sb",), 0, "", "db", ()
+    ABLATIONS = {**CoreBase.ABLATIONS,   # (timing experiments, results wrong; the trunk's cvt_pk stay under noepi: the next layer reads them)
+                 "noepi": {"perm", "cos", "pkmul", "max3", "max3r", "max3m", "max2", "mx", "pkfma", "b4a", "b4b"},
+                 "nophase": {"phload", "poff"},
+                 "nostore": {"store", "store2", "soff"},
+                 "storelate": set()}     # (correct results) an ordering experiment, see emit_epi
 
-    def e(self, op, a, text):
-        self.ins.append(Ins(op, a, text))
+    def __init__(self, auxs, feat=None, PF=5, ablate=(), save=0):
+        self.g = g = Geo(feat or self.FEAT)
+        self.NW, self.VOFF_STEP, self.AR0, self.NA, self.VL, self.VOFF, self.SOFF = g.NW, g.NW * 1024, g.AR0, g.NA, (g.VL0, g.VL1), g.VOFF, g.SOFF
+        super().__init__(auxs, g.R, PF, g.GROUP, g.FILL, ablate, save)
 
-    # ---- vmcnt bookkeeping (loads only) --------------------------------------------------------------------------------------------
-    def vm_issue(self, tag):
-        self.vm.append(tag)
-        assert len(self.vm) <= 63
+    def stage_list(self, auxs):
+        g, tiles, p = self.g, [], 0
+        for ti in range(g.LAYERS * g.MT):    # layer l (8 = bG1, 7..1 = bL_l), tile t: X -> Y -> X ...; bG1's tiles end on the d sigma_pre fragment
+            l, t = g.L0 - ti // g.MT, ti % g.MT
+            inp, out = (g.X, g.Y) if (g.L0 - l) % 2 == 0 else (g.Y, g.X)
+            b = [inp + 4 * k for k in range(g.KS)] + ([g.XS] if l == 8 else [])
+            tiles.append(Tile(p, b, 0, g.ACC[ti & 1], True, "cos", out + 8 * t, f"bL{l}.{t}", g.MT * (l - 1) + t, "v_mfma_f32_32x32x16_bf16"))
+            p += len(b)
+        assert p % g.NW == 0                 # no ragged row: the statement has no %[wave] operand
+        return tiles, p
 
-    def vm_wait(self, tag):
-        if tag not in self.vm:
-            return None
-        keep = len(self.vm) - 1 - self.vm.index(tag)
-        self.vm = self.vm[len(self.vm) - keep:] if keep else []
-        return keep
-
-    def dma_row(self, j):
+    # ---- the phase loads: the same in-order queue as the DMA rows, tagged ("ph", tile) -----------------------------------------------
+    def phase_load(self, ti):
         g = self.g
-        imm = ((g.NW * j) % self.R) * 1024
-        self.e("m0", (j,), f"s_add_u32 m0, %[wb], {imm}")
-        self.e("nop", (0,), "s_nop 0")
-        self.e("dma", (j,), f"global_load_lds_dwordx4 v{g.VOFF}, %[sb]")
-        self.e("voff", (), f"v_add_u32 v{g.VOFF}, 0x{g.NW * 1024:x}, v{g.VOFF}")
-        self.vm_issue(("row", j))
-
-    def phase_unit(self, tau):
-        g = self.g
-        l, t = g.L0 - tau // g.MT, tau % g.MT    # layer l (8 = bG1, 7..1 = bL_l) multiplies by cos(phase a_{l-1}): unit A + MT (l - 1) + t
-        return self.auxs + g.MT * (l - 1) + t
-
-    def phase_load(self, tau):
-        g = self.g
-        unit = self.phase_unit(tau)
+        unit = self.auxs + self.tiles[ti].save_unit   # layer l multiplies by cos(phase a_{l-1}): unit AUXS + MT (l - 1) + t
         delta = (unit - self.p_unit) * 1024
         self.p_unit = unit
         if delta:
-            self.e("poff", (delta,), f"v_add_u32 v{g.POFF}, 0x{delta & 0xffffffff:x}, v{g.POFF}")
-        r = g.PH0 + 4 * (tau % g.NPH)
-        self.e("phload", (r, unit), f"global_load_dwordx4 v[{r}:{r + 3}], v{g.POFF}, %[ab] nt")
-        self.vm_issue(("ph", tau))
+            self._e("poff", (delta,), f"v_add_u32 v{g.POFF}, 0x{delta & 0xffffffff:x}, v{g.POFF}")
+        r = g.PH0 + 4 * (ti % g.NPH)
+        self._e("phload", (r, unit), f"global_load_dwordx4 v[{r}:{r + 3}], v{g.POFF}, %[ab] nt")
+        self.vm.append(("ph", ti))
 
-    # ---- the epilogue of one tile: a list of closures, one instruction each ----------------------------------------------------------
-    def epilogue_items(self, tau):
-        """tile tau: accumulator ACC[tau & 1], phases PH[tau % 4]; d pre = acc * cos(2 pi u / 256) -> two bf16 B fragments of the next
+    def preamble(self):
+        for k in range(4):
+            self._e("sconst", (S_SEL[k],), f"s_mov_b32 {S_SEL[k]}, 0x{0x070c000c | (k << 8):08x}")
+        self._e("sconst", (S_B4A,), f"s_mov_b32 {S_B4A}, 0x0c0c0400")
+        self._e("sconst", (S_B4B,), f"s_mov_b32 {S_B4B}, 0x05040100")
+        self.p_unit, self.late = 0, []       # unit POFF points at (the workspace offsets start at the tile's base); (storelate) held stores
+        self.phase_load(0)
+        self.phase_load(1)
+
+    def gap_loads(self, ti, k):
+        while self.late and self.late[0][0] <= self._barriers():   # (storelate) behind the next counted wait
+            super().emit_epi("store", self.late.pop(0)[1])
+        if k == 0 and ti + 2 < len(self.tiles):
+            self.phase_load(ti + 2)
+
+    # ---- the epilogue of one tile on the shared queue; an item is one instruction, or a group that must stay together ------------------
+    def queue_epilogue(self, ti, g0):
+        """tile ti: accumulator ACC[ti & 1], phases PH[ti % 4]; d pre = acc * cos(2 pi u / 256) -> two bf16 B fragments of the next
         layer's input vector, MX8 bytes -> the dpre workspace (codec8.h: bit for bit what bpack / mx8_exponent / mx8_encode compute)"""
-        g = self.g
-        MT, TT, K43, EB, E, M, INV, MAGIC, T1, SOFF = g.MT, g.TT, g.K43, g.EB, g.E, g.M, g.INV, g.MAGIC, g.T1, g.SOFF
-        l, t = g.L0 - tau // MT, tau % MT
-        a, ph = g.ACC[tau & 1], g.PH0 + 4 * (tau % g.NPH)
-        out = (g.Y if (g.L0 - l) % 2 == 0 else g.X) + 8 * t
-        sv = g.SV[tau & 1]
-        it = []
+        g, tile = self.g, self.tiles[ti]
+        MT, TT, K43, EB, E, M, INV, MAGIC, T1 = g.MT, g.TT, g.K43, g.EB, g.E, g.M, g.INV, g.MAGIC, g.T1
+        t, a, out, ph, sv = ti % MT, tile.acc, tile.out, g.PH0 + 4 * (ti % g.NPH), g.SV[ti & 1]
 
-        def V(op, args, text):
-            it.append(lambda: self.e(op, args, text))
+        def V(op, args, text, writes=()):
+            self.epi_q.append([g0, "raw", ((op, args, text),), set(writes), a])
 
-        def group(*parts):   # several instructions that must stay together (one epilogue item)
-            it.append(lambda: [self.e(op, args, text) for op, args, text in parts])
+        def group(*parts):
+            self.epi_q.append([g0, "raw", parts, set(), a])
 
-        def wait_phase():
-            keep = self.vm_wait(("ph", tau))
-            if keep is not None:
-                self.e("waitv", (keep,), f"s_waitcnt vmcnt({keep})")
-        it.append(wait_phase)
+        self.epi_q.append([g0, "waitph", (ti,), set(), a])
         # sixteen phase bytes -> sixteen temporaries (v_perm), sixteen cosines in place, eight packed multiplies into the accumulator, eight
         # packs: every consumer sits >= 8 instructions behind its producer -- the wave issues in order, so an instruction waiting for the
         # transcendental unit (or for a packed-fp32 result) also holds back the wave's next MFMA (measured: the pair-wise pipelined order
@@ -190,19 +182,15 @@ class Trunk:
             V("perm_ph", (TT + gg, ph + (gg >> 2), gg & 3), f"v_perm_b32 v{TT + gg}, v{K43}, v{ph + (gg >> 2)}, {S_SEL[gg & 3]}")
         for gg in range(16):
             V("cos", (TT + gg,), f"v_cos_f32 v{TT + gg}, v{TT + gg}")
-        for q in range(8):
-            gg = 2 * q
+        for gg in range(0, 16, 2):
             V("pkmul", (a + gg, TT + gg), f"v_pk_mul_f32 v[{a + gg}:{a + gg + 1}], v[{a + gg}:{a + gg + 1}], v[{TT + gg}:{TT + gg + 1}]")
-        if out < A0:
+        # the output vector in AGPRs: pack into the (now dead) cosine temporaries, then eight v_accvgpr_write
+        pk = [out + q if out < A0 else TT + q for q in range(8)]
+        for q in range(8):
+            V("pk", (pk[q], a + 2 * q, a + 2 * q + 1), f"v_cvt_pk_bf16_f32 v{pk[q]}, v{a + 2 * q}, v{a + 2 * q + 1}", {pk[q]} if out < A0 else ())
+        if out >= A0:
             for q in range(8):
-                gg = 2 * q
-                V("pk", (out + q, a + gg, a + gg + 1), f"v_cvt_pk_bf16_f32 v{out + q}, v{a + gg}, v{a + gg + 1}")
-        else:   # the output vector lives in AGPRs: pack into the (now dead) cosine temporaries, then eight v_accvgpr_write
-            for q in range(8):
-                gg = 2 * q
-                V("pk", (TT + q, a + gg, a + gg + 1), f"v_cvt_pk_bf16_f32 v{TT + q}, v{a + gg}, v{a + gg + 1}")
-            for q in range(8):
-                V("accw", (out + q, TT + q), f"v_accvgpr_write_b32 {rn(out + q)}, v{TT + q}")
+                V("accw", (out + q, TT + q), f"v_accvgpr_write_b32 {rn(out + q)}, v{TT + q}", {out + q})
         # maximum of the 16 magnitudes (exact whatever the order): 8 instructions
         m, t1, t2 = M, T1, T1 + 1
         ab = lambda k: f"|v{a + k}|"  # noqa: E731
@@ -227,45 +215,21 @@ class Trunk:
             V("mx_e6", (EB + (t >> 2), E, 0, True), f"v_mov_b32 v{EB + (t >> 2)}, v{E}")
         # u = low mantissa byte of v * 2^(133 - E) + (1.5 * 2^23 + 128): two values per v_pk_fma_f32, three v_perm per four bytes; again
         # producers first (eight fmas into the sixteen temporaries), then the byte gathers
-        for q in range(8):
-            gg = 2 * q
+        for gg in range(0, 16, 2):
             V("pkfma", (TT + gg, a + gg), f"v_pk_fma_f32 v[{TT + gg}:{TT + gg + 1}], v[{a + gg}:{a + gg + 1}], v[{INV}:{INV + 1}], v[{MAGIC}:{MAGIC + 1}] op_sel_hi:[1,0,0]")
-        for q4 in range(4):
-            gg = 4 * q4
+        for gg in range(0, 16, 4):
             V("b4a", (TT + gg, TT + gg + 1, TT + gg), f"v_perm_b32 v{TT + gg}, v{TT + gg + 1}, v{TT + gg}, {S_B4A}")
             V("b4a", (TT + gg + 2, TT + gg + 3, TT + gg + 2), f"v_perm_b32 v{TT + gg + 2}, v{TT + gg + 3}, v{TT + gg + 2}, {S_B4A}")
-        for q4 in range(4):
-            gg = 4 * q4
-            V("b4b", (sv + q4, TT + gg + 2, TT + gg), f"v_perm_b32 v{sv + q4}, v{TT + gg + 2}, v{TT + gg}, {S_B4B}")
-
-        def store():
-            unit = MT * (l - 1) + t
-            delta = (unit - self.s_unit) * 1024
-            self.s_unit = unit
-            if delta:
-                self.e("soff", (delta,), f"v_add_u32 v{SOFF}, 0x{delta & 0xffffffff:x}, v{SOFF}")
-            self.e("store", (sv, unit), f"global_store_dwordx4 v{SOFF}, v[{sv}:{sv + 3}], %[db] nt")
-        store.is_store = True
-        it.append(store)
+        for gg in range(0, 16, 4):
+            V("b4b", (sv + gg // 4, TT + gg + 2, TT + gg), f"v_perm_b32 v{sv + gg // 4}, v{TT + gg + 2}, v{TT + gg}, {S_B4B}")
+        self.epi_q.append([g0, "store", (sv, tile.save_unit, 4), set(), a])
         if t == MT - 1:
-            grp = l - 1   # the layer's MT scale bytes: group l - 1 -> unit kD8Scale + (l - 1) / groups per unit, its slot of the lane's 16 bytes
-
-            def store_scale():
-                unit = g.D8_SCALE + grp // g.GROUPS_PER_UNIT
-                delta = (unit - self.s_unit) * 1024
-                self.s_unit = unit
-                off = MT * (grp % g.GROUPS_PER_UNIT)
-                self.e("soff", (delta,), f"v_add_u32 v{SOFF}, 0x{delta & 0xffffffff:x}, v{SOFF}")
-                self.e("store2", (EB, unit, off), f"global_store_dwordx{g.NEB} v{SOFF}, v[{EB}:{EB + g.NEB - 1}], %[db]" + (f" offset:{off}" if g.GROUPS_PER_UNIT > 1 else ""))
-            it.append(store_scale)
-            # largest of the lane's MT bytes, then of the wave (lane 63 after the row broadcasts), -> cell `grp` of the wave's maxima
+            grp = tile.save_unit // MT   # = l - 1.  The layer's MT scale bytes, then the largest of the lane's MT bytes and of the wave
+            self.epi_q.append([g0, "scale", (grp,), set(), a])   # (lane 63 after the row broadcasts) -> cell `grp` of the wave's maxima
             c = T1
-            n = 0
-            for r in range(g.NEB):
-                for b0 in (0, 2):
-                    dst = c + (n & 3) if n < 4 else TT + (n - 4)          # (the 512-wide layer has eight pair maxima)
-                    V("bmax", (dst, EB + r, b0, b0 + 1), f"v_max_u32_sdwa v{dst}, v{EB + r}, v{EB + r} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_{b0} src1_sel:BYTE_{b0 + 1}")
-                    n += 1
+            dsts = [c, c + 1, c + 2, c + 3, TT, TT + 1, TT + 2, TT + 3]   # (the 512-wide layer has eight pair maxima)
+            for n, (r, b0) in enumerate((r, b0) for r in range(g.NEB) for b0 in (0, 2)):
+                V("bmax", (dsts[n], EB + r, b0, b0 + 1), f"v_max_u32_sdwa v{dsts[n]}, v{EB + r}, v{EB + r} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_{b0} src1_sel:BYTE_{b0 + 1}")
             V("umax3", (c, c, c + 1, c + 2), f"v_max3_u32 v{c}, v{c}, v{c + 1}, v{c + 2}")
             V("umax", (c, c, c + 3), f"v_max_u32 v{c}, v{c}, v{c + 3}")
             if g.NEB > 2:
@@ -279,227 +243,81 @@ class Trunk:
             V("smov", (c + 1,), f"v_mov_b32 v{c + 1}, {S_MAX}")
             # one lane writes the cell; nothing else may issue while EXEC is narrowed (an A-fragment read would load one lane)
             group(("exec1", (), "s_mov_b64 exec, 1"), ("cell", (c + 1, grp), f"ds_write_b32 v{g.VCELL}, v{c + 1} offset:{4 * grp}"), ("execall", (), "s_mov_b64 exec, -1"))
-        return it
 
-    def emit_item(self, f):
-        if "storelate" in self.ablate and getattr(f, "is_store", False) and not self.last_sync_done:
+    def emit_epi(self, kind, args):
+        g = self.g
+        if kind == "raw":
+            for part in args:
+                self._e(*part)
+        elif kind == "waitph":
+            if ("ph", args[0]) in self.vm:   # (else a rendezvous' wait has covered it)
+                keep = self.vm_wait(("ph", args[0]))
+                self._e("waitv", (keep,), f"s_waitcnt vmcnt({keep})")
+        elif kind == "scale":   # group l - 1 -> unit kD8Scale + (l - 1) / groups per unit, its slot of the lane's 16 bytes
+            unit, off = g.D8_SCALE + args[0] // g.GROUPS_PER_UNIT, g.MT * (args[0] % g.GROUPS_PER_UNIT)
+            delta = (unit - self.cur_unit) * 1024
+            self.cur_unit = unit
+            self._e("soff", (delta,), f"v_add_u32 v{g.SOFF}, 0x{delta & 0xffffffff:x}, v{g.SOFF}")
+            self._e("store2", (g.EB, unit, off), f"global_store_dwordx{g.NEB} v{g.SOFF}, v[{g.EB}:{g.EB + g.NEB - 1}], %[db]" + (f" offset:{off}" if g.GROUPS_PER_UNIT > 1 else ""))
+        elif "storelate" in self.ablate and self._sync_done_for < len(self.tiles) - 1:
             # experiment (correct results): a tile's dpre store, due now, is held back until the gap behind the NEXT counted vmcnt wait (which
             # cannot tell stores from loads): it is then most of a tile old, not two MFMAs, when the following wait comes.  Its quad (SV, one of
-            # two) is not written again before the epilogue after next.
-            self.late.append([self.syncs_done + 1, f, self.cur_tile])
-            return 0
-        n0 = len(self.ins)
-        f()
-        return len(self.ins) - n0
+            # two) is not written again before the epilogue after next; flush_acc and tail let none out later than that.
+            self.late.append((self._barriers() + 1, args, self.at[0]))
+        else:
+            super().emit_epi(kind, args)
 
-    def _build(self):
-        g = self.g
-        R, PF, G, KS, MT, NW = self.R, self.PF, self.GROUP, g.KS, g.MT, g.NW
-        NT = g.LAYERS * MT                    # tiles = chunks of KS pieces (bG1's: KS + 1)
-        ks_of = lambda ti: KS + 1 if (g.g1 and ti < MT) else KS   # noqa: E731
-        mf = [(ti, k) for ti in range(NT) for k in range(ks_of(ti))]
-        first_piece = {}
-        for i, (ti, k) in enumerate(mf):
-            first_piece.setdefault(ti, i)
-        N = len(mf)
-        assert N % NW == 0
-        n_rows = N // NW
-        self.e("savem0", (), "s_mov_b32 %[m0save], m0")
-        for k in range(4):
-            self.e("sconst", (S_SEL[k],), f"s_mov_b32 {S_SEL[k]}, 0x{0x070c000c | (k << 8):08x}")
-        self.e("sconst", (S_B4A,), f"s_mov_b32 {S_B4A}, 0x0c0c0400")
-        self.e("sconst", (S_B4B,), f"s_mov_b32 {S_B4B}, 0x05040100")
-        rows_issued, pending = 0, []
+    def _barriers(self):
+        return sum(1 for x in self.ins if x.op == "barrier")
 
-        def allow_rows(free_below):
-            j = rows_issued + len(pending)
-            while j < n_rows and NW * (j + 1) - R <= free_below:
-                pending.append(j)
-                j += 1
+    def fill_cost(self, n):
+        return max(n, 1)    # FILL counts instructions here (the forward cores: items)
 
-        def emit_row():
-            nonlocal rows_issued
-            self.dma_row(pending.pop(0))
-            rows_issued += 1
+    def flush_acc(self, acc):
+        while self.late and self.late[0][2] <= self.at[0] - 2:   # (storelate) before the store quad is rewritten
+            super().emit_epi("store", self.late.pop(0)[1])
+        return super().flush_acc(acc)
 
-        def sync_for(first_tile):
-            last = min(first_tile + G, NT) - 1
-            need = (first_piece[last] + ks_of(last) + NW - 1) // NW
-            while pending:
-                emit_row()
-            assert rows_issued >= need
-            keep = self.vm_wait(("row", need - 1))
-            self.e("sync", (keep if keep is not None else len(self.vm), need), f"s_waitcnt vmcnt({keep if keep is not None else len(self.vm)})")
-            self.e("barrier", (), "s_barrier")
+    def flush_producers(self, regs, m):
+        """The last two B fragments of a layer's input are written by the previous layer's LAST epilogue, which is also the long one (scale
+        store, wave maximum: ~30 instructions more).  When the new layer's first tile reaches them (k = KS - 2) the trunk empties the
+        queue, not only up to the last cvt_pk as CoreBase would: the layer's workspace writes and its maxima cell are then complete, in
+        program order, before anything of the next layer is produced, and the next epilogue (due one tile later) starts on an empty
+        queue.  The s_nop 1 is the VALU write -> MFMA operand distance in case the producer was the last thing out."""
+        ti, k = self.at
+        if ti and ti % self.g.MT == 0 and k == self.g.KS - 2:
+            n = len(self.epi_q)
+            while self.epi_q:
+                self._pop_epi()
+            self._e("nop", (1,), "s_nop 1")
+            return n
+        assert not any(it[3] & regs for it in self.epi_q), ("B operand still in the queue", ti, k)
+        return 0
 
-        def dsread(i):
-            slot = i % R
-            base, off = (g.VL0, slot * 1024) if slot < 64 else (g.VL1, (slot - 64) * 1024)
-            d = g.AR0 + 4 * (i % g.NA)
-            self.e("dsread", (d, slot), f"ds_read_b128 {rn(d, 4)}, v{base} offset:{off}")
+    def tail(self):
+        # the last tile's epilogue has no MFMAs to hide behind: XDL write -> VALU read of a 16-pass MFMA needs 18 wait states
+        self._e("nop", (15,), "s_nop 15")
+        self._e("nop", (3,), "s_nop 3")
+        while self.epi_q:
+            self._pop_epi()
+        while self.late:
+            super().emit_epi("store", self.late.pop(0)[1])
+        self._e("waitall", (), "s_waitcnt vmcnt(0) lgkmcnt(0)")
 
-        # the workspace offsets start at the tile's base (unit 0)
-        self.p_unit, self.s_unit = 0, 0
-        allow_rows(0)
-        sync_done_for = -1
+    def header(self):
+        s = self.stats
+        return ["// GENERATED by csrc/gen/bwd_core.py -- do not edit (tests/test_bwd_core.py checks it is current).",
+                f"// dX trunk, width {self.g.feat}, AUXS = {self.auxs}: {s['mfma']} MFMAs, {s['instructions']} instructions ({s['instructions'] / s['mfma']:.2f} per MFMA), "
+                f"{s['barriers']} rendezvous, ring of {self.R} pieces, A fragments {self.PF} ahead, {self.FILL} epilogue instructions per gap"]
 
-        def read_for(i):
-            nonlocal sync_done_for
-            ti, k = mf[i]
-            if ti > sync_done_for and ti % G == 0 and k == 0:
-                sync_for(ti)
-                sync_done_for = ti + G - 1
-                return True
-            return False
-
-        self.phase_load(0)
-        self.phase_load(1)
-        for i in range(PF):
-            read_for(i)
-            dsread(i)
-        epi = []          # [earliest gap, closure, tile]
-        self.late, self.syncs_done, self.cur_tile, self.last_sync_done = [], 0, 0, False   # (storelate) deferred stores: [rendezvous count after which they go out, closure]
-        for i in range(N):
-            ti, k = mf[i]
-            l = g.L0 - ti // MT
-            inp = g.X if (g.L0 - l) % 2 == 0 else g.Y
-            acc = g.ACC[ti & 1]
-            self.cur_tile = ti
-            if k == 0:
-                while self.late and self.late[0][2] <= ti - 2:   # (storelate) no rendezvous came (the stream's end): out before its quad is rewritten
-                    self.late.pop(0)[1]()
-                # the tile before last's epilogue still reads this accumulator: it must be out (and every B fragment of a new layer
-                # is produced by the previous layer's epilogues: the last tile's runs during this tile, its two k-steps come last)
-                while epi and epi[0][2] <= ti - 2:
-                    self.emit_item(epi.pop(0)[1])
-            if ti % MT == 0 and ti > 0 and KS - 2 <= k < KS:
-                while epi and epi[0][2] < ti:
-                    self.emit_item(epi.pop(0)[1])
-                if k == KS - 2:
-                    self.e("nop", (1,), "s_nop 1")  # VALU write -> MFMA operand: two wait states
-            self.e("waitl", (min(PF - 1, N - 1 - i),), f"s_waitcnt lgkmcnt({min(PF - 1, N - 1 - i)})")
-            c = "0" if k == 0 else f"v[{acc}:{acc + 15}]"
-            areg = g.AR0 + 4 * (i % g.NA)
-            breg = inp + 4 * k if k < KS else g.XS
-            self.e("mfma", (acc, areg, breg, k == 0), f"v_mfma_f32_32x32x16_bf16 v[{acc}:{acc + 15}], {rn(areg, 4)}, {rn(breg, 4)}, {c}")
-            if k == ks_of(ti) - 1:
-                for f in self.epilogue_items(ti):
-                    epi.append([i + 2, f, ti])
-            # ---- gap(i)
-            if i + PF < N:
-                if read_for(i + PF):
-                    self.syncs_done += 1
-                    self.last_sync_done = sync_done_for >= NT - 1   # (storelate) no further rendezvous: stores go out when due again
-                    allow_rows(first_piece[ti])   # the barrier proves every wave has issued MFMA i: all tiles before the current one are consumed
-                dsread(i + PF)
-            while self.late and self.late[0][0] <= self.syncs_done:
-                self.late.pop(0)[1]()
-            if k == 0 and ti + 2 < NT:
-                self.phase_load(ti + 2)
-            if pending:
-                emit_row()
-            n = 0
-            while epi and n < self.FILL and epi[0][0] <= i:
-                n += max(self.emit_item(epi.pop(0)[1]), 1)
-        if epi:  # the last tile's epilogue has no MFMAs to hide behind: XDL write -> VALU read of a 16-pass MFMA needs 18 wait states
-            self.e("nop", (15,), "s_nop 15")
-            self.e("nop", (3,), "s_nop 3")
-        while epi:
-            self.emit_item(epi.pop(0)[1])
-        while self.late:   # (storelate) the last tiles' stores
-            self.late.pop(0)[1]()
-        assert not pending and rows_issued == n_rows
-        self.e("waitall", (), "s_waitcnt vmcnt(0) lgkmcnt(0)")
-        self.e("restm0", (), "s_mov_b32 m0, %[m0save]")
-        self._check_hazards()
-        kinds = {}
-        for x in self.ins:
-            kinds[x.op] = kinds.get(x.op, 0) + 1
-        self.stats = kinds
-
-    # ---- static checks of what the assembler would have padded in compiler-scheduled code -------------------------------------------
-    def _check_hazards(self):
-        g = self.g
-        VALU_W = {"perm_ph", "cos", "pkmul", "pk", "accw", "max3", "max3r", "max3m", "max2", "mx_e1", "mx_e2", "mx_e3a", "mx_e3", "mx_e4", "mx_e5",
-                  "mx_e6", "pkfma", "b4a", "b4b", "bmax", "umax3", "umax", "dppmax", "smov"}
-        last_cos, last_w, last_mfma_d = {}, {}, {}
-        for idx, x in enumerate(self.ins):
-            reads, writes = set(), set()
-            if x.op in VALU_W:
-                if x.op == "pkmul":
-                    a, tp = x.a
-                    reads |= {a, a + 1, tp, tp + 1}
-                    writes |= {a, a + 1}
-                elif x.op == "pkfma":
-                    d, a = x.a
-                    reads |= {a, a + 1, g.INV, g.MAGIC}
-                    writes |= {d, d + 1}
-                elif x.op == "perm_ph":
-                    writes.add(x.a[0]), reads.add(x.a[1])
-                elif x.op == "cos":
-                    writes.add(x.a[0]), reads.add(x.a[0])
-                else:
-                    regs = [r for r in x.a if isinstance(r, int)]
-                    writes.add(regs[0])
-                    reads |= set(regs[1:]) if x.op not in ("mx_e6", "bmax") else {x.a[1]}
-                    if x.op in ("mx_e1", "mx_e3a", "mx_e3", "mx_e5", "dppmax", "umax3", "umax", "max3r", "max3m", "max2"):
-                        reads.add(regs[0])
-                for r in reads:   # trans -> VALU use: at least one instruction in between
-                    assert idx - last_cos.get(r, -10) >= 2, ("trans -> VALU use", idx, x.text)
-                for r in reads:   # MFMA D -> VALU read: the tile's last MFMA at least two MFMAs back (or 18 wait states)
-                    if r in last_mfma_d:
-                        n_mf = sum(1 for y in self.ins[last_mfma_d[r] + 1:idx] if y.op == "mfma")
-                        states = sum(y.a[0] + 1 for y in self.ins[last_mfma_d[r] + 1:idx] if y.op == "nop")
-                        assert n_mf >= 2 or states >= 18, ("MFMA D -> VALU read", idx, x.text)
-                if x.op == "dppmax":
-                    assert idx - last_w.get(x.a[0], -10) >= 2 and self.ins[idx - 1].op == "nop", ("VALU write -> DPP read", idx)
-                for r in writes:
-                    last_w[r] = idx
-                    last_mfma_d.pop(r, None)
-                if x.op == "cos":
-                    last_cos[x.a[0]] = idx
-            elif x.op == "mfma":
-                acc, areg, breg, _ = x.a
-                for r in range(breg, breg + 4):
-                    d = idx - last_w.get(r, -10)
-                    nops = sum(y.a[0] + 1 for y in self.ins[max(idx - 3, 0):idx] if y.op == "nop")
-                    assert d + nops >= 3 or d >= 3, ("VALU write -> MFMA operand", idx, r)
-                for r in range(acc, acc + 16):
-                    last_mfma_d[r] = idx
-            elif x.op == "dma":
-                assert self.ins[idx - 1].op == "nop" and self.ins[idx - 2].op == "m0", ("M0 write -> LDS-DMA", idx)
-            elif x.op == "readlane":
-                assert self.ins[idx - 1].op == "nop", ("VALU write -> v_readlane", idx)
-            elif x.op == "cell":
-                assert self.ins[idx - 1].op == "exec1" and self.ins[idx + 1].op == "execall", ("EXEC narrowed around anything but the cell write", idx)
-
-    def text(self):
-        ab = self.ablate
-        drop = set()
-        if "noepi" in ab:
-            drop |= {"perm_ph", "cos", "pkmul", "max3", "max3r", "max3m", "max2", "mx_e1", "mx_e2", "mx_e3a", "mx_e3", "mx_e4", "mx_e5", "mx_e6", "pkfma",
-                     "b4a", "b4b"}
-        if "nodma" in ab:
-            drop |= {"m0", "dma", "voff"}
-        if "nophase" in ab:
-            drop |= {"phload", "poff"}
-        if "nostore" in ab:
-            drop |= {"store", "store2", "soff"}
-        return [x.text for x in self.ins if x.op not in drop]
-
-    def inc_file(self):
-        g = self.g
-        head = ["// GENERATED by csrc/gen/bwd_core.py -- do not edit (tests/test_bwd_core.py checks it is current).",
-                f"// dX trunk, width {g.feat}, AUXS = {self.auxs}: {self.stats.get('mfma', 0)} MFMAs, {len(self.ins)} instructions ({len(self.ins) / max(self.stats.get('mfma', 1), 1):.2f} per MFMA), "
-                f"{self.stats.get('barrier', 0)} rendezvous, ring of {self.R} pieces, A fragments {self.PF} ahead, {self.FILL} epilogue instructions per gap."]
-        return "\n".join(head + ['"' + t + '\\n"' for t in self.text()]) + "\n"
+    @classmethod
+    def clobber_file(cls, save=0):
+        return clobber_file(cls.FEAT)
 
 
 def clobber_file(feat=256):
     g = Geo(feat)
     regs = [r for r in range(g.XREGS if g.Y >= A0 else g.Y, g.N_VGPR) if r not in g.IN_REGS]
-    if feat == 256:
-        regs = [r for r in range(64, g.N_VGPR) if r not in g.IN_REGS]
     sregs = list(S_SEL) + [S_B4A, S_B4B, S_MAX]
     skip_a = set(range(g.XS - A0, g.XS - A0 + 4)) if g.g1 and g.XS >= A0 else set()
     return (f"// GENERATED by csrc/gen/bwd_core.py: clobber list of the dX trunk statement, width {feat} (the X vector is in/out, the constants and offsets are inputs)\n"
@@ -507,28 +325,110 @@ def clobber_file(feat=256):
             + ', "memory", "scc"\n')
 
 
-def file_names(feat, auxs, suffix=""):
-    stem = "mlp_bwd_trunk" if feat == 256 else "mlp_bwd512_trunk"
-    return f"{stem}_a{auxs}{suffix}.inc", f"{stem}_clobbers.inc"
+def file_names(feat, auxs):
+    return f"{STEM[feat]}_a{auxs}.inc", f"{STEM[feat]}_clobbers.inc"
 
 
-def main():
-    """bwd_core.py [out_dir [suffix [ablation,...]]]"""
-    out_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if len(sys.argv) > 1:
-        out_dir = sys.argv[1]
-    suffix = sys.argv[2] if len(sys.argv) > 2 else ""
-    ablate = tuple(sys.argv[3].split(",")) if len(sys.argv) > 3 else ()
-    for feat in (256, 512):
-        for auxs in (1, 2):
-            t = Trunk(auxs, feat=feat, ablate=ablate)
-            name, cname = file_names(feat, auxs, suffix)
-            with open(os.path.join(out_dir, name), "w") as f:
-                f.write(t.inc_file())
-            print(feat, auxs, len(t.ins), "instructions,", t.stats.get("mfma"), "MFMAs,", round(len(t.ins) / t.stats.get("mfma"), 2), "per MFMA")
-        with open(os.path.join(out_dir, cname), "w") as f:
-            f.write(clobber_file(feat))
+# =================================================================================================================================
+# The trunk on the shared lane model: its own ops, its initial registers, its hazard rules
+# =================================================================================================================================
+class TrunkMachine(LaneModel):
+    """TrunkMachine(trunk, stream [unit, 64, 4], acts {unit: [64, 4]}, x0 [KS][4, 64]): one wave of the workgroup, the others in lock step.
+    Besides LaneModel's checks: POFF addresses the unit loaded, no register is read while its (phase) load is in flight, VALU write ->
+    DPP read (2 wait states) and -> v_readlane (1), nothing but the cell write issues while EXEC is narrowed."""
+
+    def __init__(self, trunk, stream, acts, x0):
+        super().__init__(trunk, stream)
+        g = self.g = trunk.g
+        self.acts, self.s, self.poff, self.scale_stores, self.cells, self._wrote = acts, {}, 0, {}, {}, {}
+        for k in range(g.KS):
+            self.v[g.X + 4 * k:g.X + 4 * k + 4] = x0[k]
+        self.setf(g.MAGIC, np.full(64, 12583040.0))
+
+    def _valu(self, dst, *srcs):
+        self._valu_reads(*srcs)
+        self._wrote[dst] = self._clk
+
+    def _states_since_write(self, r):
+        return self._clk - self._wrote.get(r, -9) - 1
+
+    def own_op(self, op, a, ins):
+        g, v, f = self.g, self.v, self.f
+        if op == "sconst":
+            self.s[a[0]] = int(ins.text.split(",")[1], 16)
+        elif op == "poff":
+            self.poff += a[0]
+        elif op == "phload":
+            assert self.poff == a[1] * 1024, ("POFF does not address the unit loaded", self.poff, a[1])
+            self._valu_reads(*range(a[0], a[0] + 4))   # (the previous load of this quad has landed and been used)
+            self._vm_issue(("reg", a[0], self.acts[a[1]].T.copy()))
+        elif op == "waitv":
+            self._vm_wait(a[0])
+        elif op == "waitall":
+            self._vm_wait(0), self._lgkm_wait(0)
+        elif op == "perm_ph":
+            dst, ph, k = a
+            self._valu(dst, ph)
+            v[dst] = 0x43000000 | (((v[ph] >> np.uint32(8 * k)) & 0xFF) << 8)
+        elif op == "cos":
+            self._valu(a[0], a[0])
+            self._trans[a[0]] = self._pc
+            self.setf(a[0], np.cos(2 * np.pi * (f(a[0]).astype(np.float64) - 128.0)))
+        elif op == "pkmul":
+            for j in range(2):
+                self._valu(a[0] + j, a[0] + j, a[1] + j)
+                self.setf(a[0] + j, f(a[0] + j) * f(a[1] + j))
+        elif op in ("max3", "max3r", "max3m", "max2"):
+            self._valu(a[0], *a[1:])
+            vals = [np.abs(f(r)) if op == "max3" or (op == "max3m" and r == a[3]) else f(r) for r in a[1:]]
+            self.setf(a[0], np.maximum.reduce(vals))
+        elif op == "pkfma":
+            for j in range(2):
+                self._valu(a[0] + j, a[1] + j, g.INV, g.MAGIC)
+                self.setf(a[0] + j, f(a[1] + j).astype(np.float64) * f(g.INV).astype(np.float64) + f(g.MAGIC).astype(np.float64))
+        elif op == "b4a":   # [s1.b0, s0.b0, 0, 0]
+            self._valu(a[0], a[1], a[2])
+            v[a[0]] = (v[a[2]] & 0xFF) | ((v[a[1]] & 0xFF) << 8)
+        elif op == "b4b":   # [s1.b0, s1.b1, s0.b0, s0.b1]
+            self._valu(a[0], a[1], a[2])
+            v[a[0]] = (v[a[2]] & 0xFFFF) | ((v[a[1]] & 0xFFFF) << 16)
+        elif op == "store2":
+            assert self.soff == a[1] * 1024, ("SOFF does not address the unit stored", self.soff, a[1])
+            self.scale_stores[(a[1], a[2])] = v[a[0]:a[0] + g.NEB].T.copy()
+        elif op == "bmax":
+            self._valu(a[0], a[1])
+            v[a[0]] = np.maximum((v[a[1]] >> np.uint32(8 * a[2])) & 0xFF, (v[a[1]] >> np.uint32(8 * a[3])) & 0xFF)
+        elif op in ("umax3", "umax"):
+            self._valu(a[0], *a[1:])
+            v[a[0]] = np.maximum.reduce([v[r] for r in a[1:]])
+        elif op == "dppmax":   # row_shr:n within rows of 16; row_bcast:15 into rows 1, 3; row_bcast:31 into rows 2, 3
+            assert self._states_since_write(a[0]) >= 2, ("VALU write -> DPP read needs two wait states", ins.text)
+            self._valu(a[0], a[0])
+            if a[1].startswith("row_shr:"):
+                n = int(a[1].split(":")[1])
+                src = np.where((LANE & 15) >= n, LANE - n, LANE)
+            elif a[1].startswith("row_bcast:15"):
+                src = np.where((LANE >> 4) & 1, (LANE & ~15) - 1, LANE)
+            else:
+                src = np.where(LANE >= 32, 31, LANE)
+            v[a[0]] = np.maximum(v[a[0]], v[a[0]][src])
+        elif op == "readlane":
+            assert self._states_since_write(a[0]) >= 1, ("VALU write -> v_readlane needs one wait state", ins.text)
+            self.s[S_MAX] = int(v[a[0]][63])
+        elif op == "smov":
+            self._valu(a[0])
+            v[a[0]] = self.s[S_MAX]
+        elif op == "exec1":
+            self._exec1 = True
+        elif op == "cell":
+            assert self._exec1
+            self.cells[a[1]] = int(v[a[0]][0])
+            self.pending.append((None, None, None, None))   # an LDS write in the in-order queue of the reads
+        elif op == "execall":
+            self._exec1 = False
+        else:
+            super().own_op(op, a, ins)
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(max(main(type(f"Trunk{feat}", (Trunk,), {"FEAT": feat}), STEM[feat], __doc__, PF=5) or 0 for feat in STEM))

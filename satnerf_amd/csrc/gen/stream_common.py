@@ -1,17 +1,21 @@
-"""What the forward-core generators (fwd_core.py, fwd_core3.py, fwd_core512.py) share: the instruction record, the unified register
-naming, the bf16 / fragment helpers, ONE scheduler (``CoreBase``) and ONE lane-accurate CPU model (``LaneModel``).  A core states only
-what is different about it (register map, stage list, waves per workgroup, requests per DMA row, MFMAs per k-step, its epilogue recipe,
-file header and clobber list); every core's stream is held to the same set of checks.
+"""What the generators of the ring-fed MFMA streams share -- the forward cores (fwd_core.py, fwd_core3.py, fwd_core512.py) and the dX trunk
+(bwd_core.py): the instruction record, the unified register naming, the bf16 / fragment helpers, ONE scheduler (``CoreBase``) and ONE
+lane-accurate CPU model (``LaneModel``).  A core states only what is different about it (register map, stage list, waves per workgroup,
+requests per DMA row, MFMAs per k-step, its epilogue recipe, its other loads, head and tail, file header and clobber list); every core's
+stream is held to the same set of checks.
 
 Structure of a core (one wave = 32 points; mlp_layout.h for the stream format):
   * k-step i of the wave consumes unit i of the stream (one 1-KiB A fragment per plane = one k-step of one 32-row output tile).  Units
     reach LDS by LDS-DMA "rows" of NW units (REQS 1-KiB requests per wave and row) into a flat ring of R units; ``sync`` points (counted
     vmcnt + s_barrier) every GROUP tiles make a group's units visible, after which the rows whose ring slots are free are requested.
   * A fragments are fetched PF k-steps ahead (ds_read_b128 into a ring of register quads, counted lgkmcnt before each MFMA).
+  * loads retire in order, so every vmcnt is a count of the LOADS (DMA requests, a core's own register loads) issued behind the one
+    waited for, read off one tagged queue; stores are left out (they may complete out of order: a wait can only get longer).
   * the epilogue of tile t-1 is spread over the gaps of tile t's MFMAs, starting two MFMAs after the tile's last one (XDL write -> VALU
-    read needs 12 wait states).
+    read: LaneModel.XDL_NOPS wait states).
   * hazards the assembler does not pad inside inline asm are handled here and checked by the model: trans -> VALU use (1 state), VALU
-    write -> MFMA operand (2 states), MFMA D -> VALU read (>= 2 MFMAs later), M0 write -> LDS-DMA (1 state).
+    write -> MFMA operand (2 states), MFMA D -> VALU read (>= 2 MFMAs later), M0 write -> LDS-DMA (1 state); the trunk's model adds
+    VALU write -> DPP read (2) and -> v_readlane (1); nothing but the trunk's cell write issues while EXEC is narrowed.
 """
 from __future__ import annotations
 
@@ -60,13 +64,16 @@ class CoreBase:
     """A subclass sets: NW (waves per workgroup = units per DMA row), PRE_ROWS (rows the kernel prologue wrote into the ring), SRC (the
     stream operand of each of a row's requests: one per plane), VOFF_STEP, LABEL, SYNC_AHEAD, PK, MT / MTH (tiles of a trunk / head
     layer), SAVE, AR0 / NA, OUT_HEAD and its register map (VL, VOFF, SIG, TMP, SV, SOFF, KMAGIC, EB, MXT, K128, SCALE_DWORDS), and defines
-    stage_list(), header(), clobber_file() (and preamble() / a_frags() / mfmas() / queue_dense() / emit_epi() where it differs)."""
+    stage_list(), header(), clobber_file() (and preamble() / a_frags() / mfmas() / queue_dense() / emit_epi() / gap_loads() / fill_cost() /
+    flush_producers() / tail() where it differs)."""
 
     PRE_ROWS = 0          # rows 0 .. PRE_ROWS - 1: in the ring before the stream starts, never requested
     SYNC_AHEAD = False    # the rendezvous a prefetch needs goes in front of the k-step's first MFMA (True) or into the gap behind it
     PK = "PK"             # the cvt_pk mnemonic (a macro where the kernel chooses bf16 / f16)
     OUT_HEAD = None       # VGPRs the head accumulator is copied to at the end when it lives in AGPRs
     TMP = ()
+    WS = "ab"             # the workspace operand of the stores
+    KEEP_FIRST = ("m0", "dma", "voff")   # what `nodma` leaves in front of the first rendezvous (the first reads need those requests)
 
     def __init__(self, auxs, R, PF, GROUP, FILL, ablate, save):
         assert R % self.NW == 0 and R * 1024 * len(self.SRC) <= 65536 * len(self.VL) and PF + 1 <= self.NA and save in (0, self.SAVE)
@@ -108,10 +115,21 @@ class CoreBase:
         self._e("m0", (j, plane), f"s_add_u32 m0, %[wb], {imm}")
         self._e("nop", (0,), "s_nop 0")
         self._e("dma", (j, plane, partial), f"global_load_lds_dwordx4 v{self.VOFF}, %[{self.SRC[plane]}]")
+        self.vm.append(("row", j))
         if plane == planes - 1:
             if partial is not None:
                 self._e("label", (j,), f"{label}:")
             self._e("voff", (), f"v_add_u32 v{self.VOFF}, 0x{self.VOFF_STEP:x}, v{self.VOFF}")
+
+    # ---- the loads in flight, oldest first: ("row", j) per DMA request, a core's own tags for its register loads --------------------------
+    def vm_wait(self, tag):
+        """the vmcnt that lets the newest load tagged `tag` and everything older land: the loads issued behind it.  A wave that skips the
+        ragged last row has that row's requests fewer in flight, and the count must hold for it too."""
+        if tag in self.vm:
+            del self.vm[:len(self.vm) - self.vm[::-1].index(tag)]
+        vm = sum(1 for t in self.vm if t != ("row", self.partial_row))
+        assert vm <= 63
+        return vm
 
     # ---- ring / DMA-row bookkeeping ------------------------------------------------------------------------------------------------
     def allow_rows(self, free_below):
@@ -135,19 +153,14 @@ class CoreBase:
             self.rows_issued += 1
 
     def sync_for(self, first_tile):
-        T, NW, planes = self.tiles, self.NW, len(self.SRC)
+        T, NW = self.tiles, self.NW
         last = min(first_tile + self.GROUP, len(T)) - 1
         need = (T[last].p0 + T[last].n + NW - 1) // NW  # rows 0 .. need-1 must have landed
         # every row allowed so far is emitted before the wait (program order = count order)
         while self.pending_rows:
             self.emit_request()
-        issued = self.rows_issued
-        assert issued >= need, (first_tile, issued, need)
-        vm = planes * (issued - max(need, self.PRE_ROWS))
-        if self.partial_row is not None and issued > self.partial_row and need <= self.partial_row:
-            vm -= planes  # waves that skipped the ragged row have one row's requests fewer in flight
-        vm = max(vm, 0)
-        assert vm <= 63
+        assert self.rows_issued >= need, (first_tile, self.rows_issued, need)
+        vm = self.vm_wait(("row", need - 1))
         self._e("sync", (vm, need), f"s_waitcnt vmcnt({vm})")
         self._e("barrier", (), "s_barrier")
 
@@ -271,7 +284,7 @@ class CoreBase:
             delta = (unit - self.cur_unit) * 1024
             self.cur_unit = unit
             self._e("soff", (delta,), f"v_add_u32 v{self.SOFF}, 0x{delta & 0xffffffff:x}, v{self.SOFF}")
-            self._e("store", (reg, unit, ndw), f"global_store_dwordx{ndw} v{self.SOFF}, {rn(reg, ndw)}, %[ab]" + (" nt" if kind == "store" else ""))
+            self._e("store", (reg, unit, ndw), f"global_store_dwordx{ndw} v{self.SOFF}, {rn(reg, ndw)}, %[{self.WS}]" + (" nt" if kind == "store" else ""))
         elif kind == "mx_max":
             a, g, first = args
             m = self.MXT
@@ -302,9 +315,11 @@ class CoreBase:
 
     def _pop_epi(self):
         _, kind, args, writes, _ = self.epi_q.pop(0)
+        n0 = len(self.ins)
         self.emit_epi(kind, args)
         for r in writes:
             self.written_at[r] = len(self.ins) - 1
+        return len(self.ins) - n0
 
     def flush_producers(self, regs, m):
         """MFMA m is about to read `regs`: everything in the queue up to the last instruction that writes one of them must be emitted now"""
@@ -328,7 +343,23 @@ class CoreBase:
             self._e("nop", (3 - dist,), f"s_nop {3 - dist}")
 
     def preamble(self):
-        """moves of operands that arrive in VGPRs and live in AGPRs"""
+        """what stands in front of the first DMA request: moves of operands that arrive in VGPRs and live in AGPRs, constants, first loads"""
+
+    def gap_loads(self, ti, k):
+        """a core's own loads in the gap behind k-step k of tile ti, in front of the gap's DMA request"""
+
+    def fill_cost(self, n):
+        """what an epilogue item that emitted n instructions counts against FILL"""
+        return 1
+
+    def tail(self):
+        """behind the last MFMA: the head accumulator is read right behind it (by compiler code or here)"""
+        assert not self.epi_q
+        self._e("nop", (15,), "s_nop 15")
+        if self.OUT_HEAD is not None:
+            self._e("nop", (3,), "s_nop 3")
+            for g in range(16):
+                self._e("accr", (self.OUT_HEAD + g, self.HEAD + g), f"v_accvgpr_read_b32 v{self.OUT_HEAD + g}, {rn(self.HEAD + g)}")
 
     def a_frags(self, i):
         """(register quad, plane) of the A fragments of k-step i, in read order"""
@@ -349,6 +380,7 @@ class CoreBase:
         self.partial_n = N % NW
         self.rows_issued = self.PRE_ROWS
         self.pending_rows, self._plane = [], 0   # rows allowed but not yet (wholly) requested, plane of the next request
+        self.vm = []
         self.epi_q, self.n_saves, self.cur_unit = [], 0, 0
         self.written_at = {}   # register -> index in self.ins of the VALU instruction that last wrote it (B operands only)
         self.trans_at = {}     # VGPR -> index of a v_sin that wrote it
@@ -363,7 +395,7 @@ class CoreBase:
                 self.dsread(*rd)
         m = forced = 0  # MFMA index, epilogue instructions emitted ahead of their gap
         for i in range(N):
-            ti, k = ks[i]
+            self.at = ti, k = ks[i]
             t = T[ti]
             aregs = [reg for reg, _ in self.a_frags(i)]
             ops = self.mfmas(t, k, aregs)  # (A quad, B quad) of the k-step's MFMAs
@@ -389,18 +421,15 @@ class CoreBase:
                 if p < len(reads):
                     self.dsread(*reads[p])
                     in_gaps += 1
-                if p == len(ops) - 1 and self.pending_rows:
-                    self.emit_request()
+                if p == len(ops) - 1:
+                    self.gap_loads(ti, k)
+                    if self.pending_rows:
+                        self.emit_request()
                 n = 0
                 while self.epi_q and n < self.FILL and self.epi_q[0][0] <= m - 1:
-                    self._pop_epi()
-                    n += 1
-        assert not self.epi_q and not self.pending_rows and self.rows_issued == self.n_rows
-        self._e("nop", (15,), "s_nop 15")  # the head accumulator is read right behind the last MFMA (by compiler code or just below)
-        if self.OUT_HEAD is not None:
-            self._e("nop", (3,), "s_nop 3")
-            for g in range(16):
-                self._e("accr", (self.OUT_HEAD + g, self.HEAD + g), f"v_accvgpr_read_b32 v{self.OUT_HEAD + g}, {rn(self.HEAD + g)}")
+                    n += self.fill_cost(self._pop_epi())
+        assert not self.pending_rows and self.rows_issued == self.n_rows
+        self.tail()
         self._e("restm0", (), "s_mov_b32 m0, %[m0save]")
         self.stats = dict(mfma=m, instructions=len(self.ins), forced_epilogue=forced, rows=self.n_rows,
                           barriers=sum(1 for x in self.ins if x.op == "barrier"), nops=sum(1 for x in self.ins if x.op == "nop"))
@@ -429,7 +458,7 @@ class CoreBase:
         for x in self.ins:
             if x.op == "sync":
                 seen_first_sync = True
-            if x.op.partition("_")[0] in drop and (seen_first_sync or x.op not in ("m0", "dma", "voff")):
+            if x.op.partition("_")[0] in drop and (seen_first_sync or x.op not in self.KEEP_FIRST):
                 continue
             out.append(x.text)
         return out
@@ -448,20 +477,20 @@ def main(cls, stem, doc, **defaults):
 
     ap = argparse.ArgumentParser(description=doc)
     ap.add_argument("--out", default=None, help="output directory (default: csrc/)")
-    ap.add_argument("--ablate", default="", help="comma list of timing ablations: " + ",".join(CoreBase.ABLATIONS))
+    ap.add_argument("--ablate", default="", help="comma list of timing ablations: " + ",".join(cls.ABLATIONS))
     for name, value in defaults.items():
         ap.add_argument("--" + name, type=int, default=value)
     a = ap.parse_args()
     out_dir = a.out or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     os.makedirs(out_dir, exist_ok=True)
     for auxs in (1, 2):
-        for save in (0, cls.SAVE):
+        for save in sorted({0, cls.SAVE}):
             c = cls(auxs, ablate=[x for x in a.ablate.split(",") if x], save=save, **{name: getattr(a, name) for name in defaults})
             path = os.path.join(out_dir, f"{stem}_a{auxs}{f's{save}' if save else ''}.inc")
             with open(path, "w") as f:
                 f.write(c.inc_file())
             print(path, c.stats)
-    for save in (0, cls.SAVE):
+    for save in sorted({0, cls.SAVE}):
         with open(os.path.join(out_dir, f"{stem}_clobbers{f'_s{save}' if save else ''}.inc"), "w") as f:
             f.write(cls.clobber_file(save))
 
@@ -505,9 +534,15 @@ class LaneModel:
       * ring protocol: a unit is read only after a rendezvous that covers its row; a ring slot is overwritten only once the MFMAs that
         consume its previous content have been issued ahead of a barrier (by this wave; the barrier extends that to all waves), and
         not while a read of it is in flight;
-      * vmcnt lets no needed request stay in flight, for waves that take and waves that skip the ragged last row; lgkmcnt lets no A
-        fragment an MFMA reads stay in flight; VOFF addresses row j when row j is requested; SOFF addresses the unit stored;
-      * hazards: XDL write -> VALU read, trans -> VALU use, VALU write -> MFMA operand, M0 write -> LDS-DMA."""
+      * loads retire in order (a real queue, for waves that take and waves that skip the ragged last row): vmcnt lets no needed request
+        stay in flight, no register is read while a load into it is; lgkmcnt lets no A fragment an MFMA reads stay in flight; VOFF
+        addresses row j when row j is requested; SOFF addresses the unit stored;
+      * hazards: XDL write -> VALU read, trans -> VALU use, VALU write -> MFMA operand, M0 write -> LDS-DMA; between a narrowing of
+        EXEC and its restoring nothing issues but the one-lane LDS write it is for (the trunk's `cell`).
+    A core's model adds the ops that are its own in ``own_op``."""
+
+    XDL_NOPS = 18            # XDL write -> VALU read behind an s_nop chain: wait states after a 16-pass MFMA
+    IGNORED = {"savem0", "restm0", "dma_pred", "dma_br", "label"}
 
     def __init__(self, core, *planes):
         c = self.c = core
@@ -519,20 +554,20 @@ class LaneModel:
         self.synced_rows = c.PRE_ROWS
         self.uses = np.zeros(c.n_pieces, np.int32)   # MFMAs issued on the unit
         self.consumed_before_barrier = np.zeros(c.n_pieces, bool)
-        self.pending = []        # reads in flight: (dst, slot, plane, unit)
+        self.pending = []        # LDS reads in flight, oldest first: (dst, slot, plane, unit)
         self.ar = {}             # register quad -> (unit, plane) it holds
-        self.issued = {"full": [], "skip": []}  # requests (row, plane) of a wave that takes / skips the ragged last row
+        # loads in flight, oldest first, of a wave that takes / skips the ragged last row: ("row", j, plane) or ("reg", first register, data [n, 64])
+        self.vmq = {"full": [], "skip": []}
         for u in range(c.PRE_ROWS * c.NW):  # in the ring when the stream starts (the prologue wrote them, then a barrier)
             for pl, s in enumerate(planes):
                 self.ring_unit[u][pl], self.ring[u, pl] = u, s[u]
-        for reqs in self.issued.values():
-            reqs += [(r, pl) for r in range(c.PRE_ROWS) for pl in range(len(planes))]
         self.voff_rows = 0       # rows VOFF has been advanced by: the source of the next request is stream unit NW * voff_rows + wave
         self.soff = 0            # saving cores: byte offset of SOFF relative to the tile's workspace base
         self.stores = {}         # unit -> [4, 64] uint32 (or [2, 64] for a two-dword scale unit)
         self.last_write = {}     # register -> index of the VALU instruction that wrote it (cvt_pk, moves)
         self._xdl, self._n_mfma, self._nops = {}, 0, 0
-        self._trans, self._pc, self._m0_at = {}, 0, -9  # v_sin results, instruction index, last M0 write
+        self._trans, self._pc, self._m0_at = {}, 0, -9  # v_sin / v_cos results, instruction index, last M0 write
+        self._clk, self._exec1 = 0, False               # wait states issued so far (an instruction is one, s_nop n is n + 1), EXEC narrowed
 
     def f(self, r):
         return self.v[r].view(np.float32)
@@ -554,14 +589,40 @@ class LaneModel:
     def _valu_reads(self, *regs):
         for r in regs:
             k = self._xdl.get(r)
-            assert k is None or self._n_mfma - 1 - k >= 2 or self._nops >= 12, ("VALU reads an MFMA result too early", r)
+            assert k is None or self._n_mfma - 1 - k >= 2 or self._nops >= self.XDL_NOPS, ("VALU reads an MFMA result too early", r)
             assert self._pc - self._trans.get(r, -9) >= 2, ("trans result used by the next instruction", r)  # trans -> VALU: 1 wait state
+            assert not any(e[0] == "reg" and e[1] <= r < e[1] + len(e[2]) for e in self.vmq["full"]), ("register read while its load is in flight", r)
+
+    def _vm_issue(self, entry, ragged=False):
+        self.vmq["full"].append(entry)
+        if not ragged:
+            self.vmq["skip"].append(entry)
+
+    def _vm_wait(self, keep):
+        for q in self.vmq.values():  # loads return in order: all but the `keep` newest have landed
+            for e in q[:max(len(q) - keep, 0)]:
+                if e[0] == "reg":
+                    self.v[e[1]:e[1] + len(e[2])] = e[2]
+            del q[:max(len(q) - keep, 0)]
+
+    def _lgkm_wait(self, keep):
+        while len(self.pending) > keep:
+            dst, slot, plane, unit = self.pending.pop(0)
+            if dst is not None:  # (None: an LDS write)
+                assert self.ring_unit[slot][plane] == unit, "ring slot overwritten while a read of it was in flight"
+                self.v[dst:dst + 4] = self.ring[slot, plane].T
+                self.ar[dst] = (unit, plane)
+
+    def own_op(self, op, a, ins):
+        assert op in self.IGNORED, "instruction not modelled: " + ins.text
 
     def run(self):
         c, NW = self.c, self.c.NW
         for n, ins in enumerate(c.ins):
             op, a = ins.op, ins.a
             self._pc = n
+            self._clk += 1
+            assert not self._exec1 or op in ("cell", "execall"), ("instruction issued with EXEC narrowed to one lane", ins.text)
             if op == "mfma":
                 acc, areg, breg, c0 = a
                 assert not any(d == areg for d, *_ in self.pending), "MFMA reads an A fragment still in flight"
@@ -583,22 +644,19 @@ class LaneModel:
                 self._mfma_wrote(acc)
             elif op == "nop":
                 self._nops += a[0] + 1
+                self._clk += a[0]
             elif op == "dsread":
                 dst, slot, plane = a
                 unit = self.ring_unit[slot][plane]
                 assert unit >= 0 and unit // NW < self.synced_rows, ("unit read before the rendezvous that covers its row", unit, self.synced_rows)
                 self.pending.append((dst, slot, plane, unit))
             elif op == "waitl":
-                while len(self.pending) > a[0]:
-                    dst, slot, plane, unit = self.pending.pop(0)
-                    assert self.ring_unit[slot][plane] == unit, "ring slot overwritten while a read of it was in flight"
-                    self.v[dst:dst + 4] = self.ring[slot, plane].T
-                    self.ar[dst] = (unit, plane)
+                self._lgkm_wait(a[0])
             elif op == "sync":
                 vm, need = a
-                for cls, reqs in self.issued.items():  # loads return in order: all but the vm newest requests have landed
-                    landed = set(reqs[:max(len(reqs) - vm, 0)])
-                    missing = [q for q in reqs if q[0] < need and q not in landed]
+                self._vm_wait(vm)
+                for cls, q in self.vmq.items():
+                    missing = [e for e in q if e[0] == "row" and e[1] < need]
                     assert not missing, ("vmcnt lets a needed request stay in flight", cls, vm, need, missing[:4])
                 self.synced_rows = max(self.synced_rows, need)
             elif op == "barrier":
@@ -609,9 +667,7 @@ class LaneModel:
                 j, plane, partial = a
                 assert n - self._m0_at >= 2, "M0 write -> LDS-DMA needs one wait state"
                 assert c.PRE_ROWS + self.voff_rows == j, ("VOFF does not address row j of the stream", j, self.voff_rows)
-                self.issued["full"].append((j, plane))
-                if partial is None:
-                    self.issued["skip"].append((j, plane))
+                self._vm_issue(("row", j, plane), ragged=partial is not None)
                 for w in range(NW if partial is None else partial):
                     u = NW * j + w
                     slot = u % c.R
@@ -670,8 +726,10 @@ class LaneModel:
                 self.setf(a[0], self.f(a[0]).astype(np.float64) * 0.0078125 + self.f(a[0]).astype(np.float64))
             elif op == "mx_e2":
                 self.v[a[0]] = self.v[a[1]] >> np.uint32(23)
-            elif op == "mx_e3":  # (with mx_e3a in front of it: the clamp)
-                self.v[a[0]] = np.clip(self.v[a[0]], 6, 254).astype(np.uint32)
+            elif op == "mx_e3a":  # clamp to [6, 254]
+                self.v[a[0]] = np.maximum(self.v[a[0]], np.uint32(6))
+            elif op == "mx_e3":
+                self.v[a[0]] = np.minimum(self.v[a[0]], np.uint32(254))
             elif op == "mx_e4":
                 self.v[a[0]] = (np.uint32(260) - self.v[a[1]]).astype(np.uint32)
             elif op == "mx_e5":
@@ -686,4 +744,6 @@ class LaneModel:
             elif op == "mx_q2":  # v_cvt_pk_u8_f32: round to nearest even, saturate to [0, 255]
                 d, t, byte = a
                 self._set_byte(d, byte, np.clip(np.rint(self.f(t).astype(np.float64)), 0, 255).astype(np.uint32))
+            else:
+                self.own_op(op, a, ins)
         assert (self.uses == self.uses_per_unit).all()

@@ -18,6 +18,8 @@ import pytest
 
 from oracle import satnerf_oracle as O
 from tests import mfma_emulator as E
+from tests.stream_edits import (_moved, _mut_b_operand, _mut_barriers, _mut_lgkmcnt, _mut_m0_nop, _mut_soff, _mut_sync_rows, _mut_vmcnt,
+                                _mut_voff, _nth, _steady)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -232,75 +234,10 @@ def test_width512_core_stream_computes_the_forward_pass(tau, save):
 CORES = {"fwd_core": ("Core", "Machine", 8, 1), "fwd_core3": ("Core3", "Machine3", 16, 2), "fwd_core512": ("Core512", "Machine512", 8, 1)}
 
 
-def _nth(ins, op, n, start=0):
-    """index of the n-th (from 0) instruction of kind `op` at or after `start`"""
-    return [i for i in range(start, len(ins)) if ins[i].op == op][n]
-
-
-def _moved(ins, src, dst):
-    """the list with instruction `src` taken out and put back so that it stands directly in front of what was instruction `dst`"""
-    out = list(ins)
-    x = out.pop(src)
-    out.insert(dst - (src < dst), x)
-    return out
-
-
-def _with_args(ins, i, a):
-    out = list(ins)
-    out[i] = copy.copy(ins[i])
-    out[i].a = a
-    return out
-
-
-def _steady(ins):
-    """where the edits are made: behind the third rendezvous, in the regular part of the stream"""
-    return _nth(ins, "barrier", 2)
-
-
-def _mut_lgkmcnt(ins):
-    i = _nth(ins, "waitl", 0, _steady(ins))
-    return _with_args(ins, i, (ins[i].a[0] + 1,))
-
-
-def _mut_vmcnt(ins):
-    i = _nth(ins, "sync", 0, _steady(ins))
-    return _with_args(ins, i, (ins[i].a[0] + 8, ins[i].a[1]))
-
-
-def _mut_m0_nop(ins):
-    i = _nth(ins, "m0", 0, _steady(ins))
-    assert ins[i + 1].op == "nop" and ins[i + 2].op == "dma"
-    return ins[:i + 1] + ins[i + 2:]
-
-
-def _mut_barriers(ins):
-    s = _steady(ins)
-    return [x for i, x in enumerate(ins) if i <= s or x.op != "barrier"]
-
-
-def _mut_sync_rows(ins):
-    i = _nth(ins, "sync", 0, _steady(ins))
-    return _with_args(ins, i, (ins[i].a[0], ins[i].a[1] - 2))
-
-
 def _mut_sigma_mov(ins):
     i = _nth(ins, "mov", 0)
     last = max(k for k in range(i) if ins[k].op == "mfma" and ins[k].a[0] == ins[i].a[1])
     return _moved(ins, i, last + 1)
-
-
-def _mut_b_operand(ins):
-    """the cvt_pk / v_accvgpr_write closest to the MFMA that reads the B operand it writes, moved to directly in front of that MFMA"""
-    writer, best = {}, None
-    for i in range(_steady(ins), len(ins)):
-        x = ins[i]
-        if x.op in ("pk", "accw"):
-            writer[x.a[0]] = i
-        elif x.op == "mfma":
-            w = max(writer.get(r, -1) for r in range(x.a[2], x.a[2] + 4))
-            if w >= 0 and (best is None or i - w < best[1] - best[0]):
-                best = (w, i)
-    return _moved(ins, *best)
 
 
 def _mut_trans(ins):
@@ -312,16 +249,6 @@ def _mut_trans(ins):
             sin_at[x.a[0]] = i
         elif x.op == "pk" and x.a[2] in sin_at:
             return _moved(ins, i, sin_at[x.a[2]] + 1)
-
-
-def _mut_voff(ins):
-    i = _nth(ins, "voff", 0, _steady(ins))
-    return ins[:i] + ins[i + 1:]
-
-
-def _mut_soff(ins):
-    i = _nth(ins, "soff", 2)
-    return ins[:i] + ins[i + 1:]
 
 
 MUTATIONS = {
