@@ -406,6 +406,28 @@ int sr_points_along(const float* rays, int ray_stride, int dir_col, const float*
  * [sin(2^0 x), cos(2^0 x), sin(2^1 x), cos(2^1 x), ...], no identity term */
 int sr_positional_map(const float* x, int ld, int dim, int64_t rows, int n_freqs, float* out, void* stream);
 
+/* ---- fused classic NeRF forward (csrc/nerf_fwd.inc): inference, width 256, single-pass bf16 operands with fp32 accumulation ----------
+ * The model of models/__init__.py:8: mapping_sizes [10, 4], 8 layers of 256, skip at layer 4.  `stream_hi` = the weights packed by
+ * sr_pack_stream with the gather maps of satnerf_amd/packing.py: nerf_forward_maps; sr_nerf_stream_elems(feat) = its bf16 element count,
+ * -1 for a width this build does not serve.
+ *
+ * sr_nerf_mlp_fwd replaces NeRF.forward with both Mapping.forward calls (models/nerf.py:184-227) for n_points points:
+ *   xyz (P, xyz_stride >= 3) per point, dirs read at row p / row_div (1 = a direction per point, n_samples = per ray);
+ *   rgb (P,3) = sigmoid(.) * 1.002 - 0.001, sigma (P) = softplus(.).
+ * sr_nerf_render_fwd replaces one pass of models/nerf.py:71-133 with the sampling in front of it (rendering.py:62-81,110-112,153-154) for
+ * n_rays rays (N, ray_stride >= 8) = o d near far: depths = the stratified depths of sr_ray_sample_fwd from u (N,S), bit for bit, or z_in
+ * (N,S) as given (exactly one of the two); points o + d z; the network; classic compositing = sr_composite_fwd without sun, sky and clamp
+ * (noise (N,S) may be NULL).  Writes weights, transparency (N,S) and, where not NULL, z_out (N,S), rgb (N,3), depth (N).
+ * A workgroup composites whole rays of its 256 points: 2 <= n_samples <= sr_nerf_render_max_samples().
+ * Unsupported arguments return an error and launch nothing; zero points / rays return 0 without a launch. */
+int64_t sr_nerf_stream_elems(int feat);
+int sr_nerf_render_max_samples(void);
+int sr_nerf_mlp_fwd(const float* xyz, int xyz_stride, const float* dirs, int dir_stride, int row_div, int64_t n_points, int feat,
+                    const uint16_t* stream_hi, float* rgb, float* sigma, void* stream);
+int sr_nerf_render_fwd(const float* rays, int ray_stride, int64_t n_rays, int n_samples, const float* u, const float* z_in,
+                       const float* noise, float noise_std, int feat, const uint16_t* stream_hi, float* z_out, float* rgb, float* depth,
+                       float* weights, float* transparency, void* stream);
+
 /* ---- whole-image evaluation -------------------------------------------------------------
  * sr_composite_image: compositing (models/satnerf.py:52-70) that keeps per ray only what
  * eval_satnerf.save_nerf_output_to_images writes per pixel (eval_satnerf.py:106-146): image (N,13) =

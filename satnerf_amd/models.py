@@ -350,8 +350,9 @@ class ShadowNeRF(SatNeRF):
 
 class NeRF(_FlatParamModule):
     """Classic NeRF (models/nerf.py:135-227): positional encoding, ReLU trunk, direction-conditioned colour head; same
-    ``state_dict`` keys.  BASELINE configs[0] is a CPU plumbing run in the reference; here it runs layer by layer through the
-    same MFMA GEMM as the non-256 Sat-NeRF widths (satnerf_amd.generic)."""
+    ``state_dict`` keys.  BASELINE configs[0] is a CPU plumbing run in the reference; here a no-grad forward in ``bf16`` at the shape of
+    models/__init__.py:8 runs in one fused launch (csrc/nerf_fwd.inc), everything else -- the other modes and shapes, training -- layer
+    by layer through the same MFMA GEMM as the non-256 Sat-NeRF widths (satnerf_amd.generic)."""
 
     number_of_outputs = 4
     fused = False
@@ -375,12 +376,44 @@ class NeRF(_FlatParamModule):
         self.rgb_from_xyzdir = nn.Sequential(nn.Linear(feat + in_dir, feat // 2), nl, nn.Linear(feat // 2, 3), nn.Sigmoid())
         self._flatten()
 
-    def forward(self, input_xyz, input_dir=None, sigma_only=False):
+    def fused_forward(self, mode):
+        """True when a no-grad forward in numeric mode ``mode`` runs in the one-launch kernel (csrc/nerf_fwd.inc): ``bf16`` at the shape
+        of models/__init__.py:8.  Every other mode and shape runs layer by layer (satnerf_amd.generic)."""
+        return ops.nerf_fused_ok(self, mode)
+
+    def packed(self, mode):
+        """The bf16 weight stream of the fused kernel for the current weights; rebuilt only when the flat buffer changed."""
+        if not self.fused_forward(mode):
+            raise ValueError(f"no fused classic NeRF for mode {mode!r}, feat={self.feat}, layers={self.layers}, skips={self.skips}")
+        flat = self.flat_params()
+        if not flat.is_cuda:
+            raise RuntimeError("NeRF parameters are on the CPU: move the model to the GPU (.cuda()); there is no CPU path")
+        key = _stream_kind(mode)
+        ent = self._pack_cache.get(key)
+        version = self.weights_version()
+        if ent is not None and ent[0] == version and ent[1] == flat.data_ptr():
+            return ent[2]
+        maps = self._pack_cache.get("maps")
+        if maps is None or maps["idx"].device != flat.device:
+            m = packing.nerf_forward_maps(self.feat)
+            maps = {k: torch.from_numpy(m[k]).to(flat.device) for k in ("idx", "scale")}
+            self._pack_cache["maps"] = maps
+        hi, _ = ops.pack_stream(flat, maps["idx"], maps["scale"], want_lo=False)
+        self._pack_cache[key] = (version, flat.data_ptr(), hi)
+        return hi
+
+    def forward(self, input_xyz, input_dir=None, sigma_only=False, mlp_mode=None):
         from .generic import nerf_points
+        from .rendering import default_mode
 
         if input_dir is None and not sigma_only:
             raise TypeError("NeRF.forward needs input_dir (models/nerf.py:213)")
         xyz = input_xyz.contiguous().float()
+        if self.fused_forward(mlp_mode or default_mode()):
+            d = xyz if input_dir is None else input_dir.contiguous().float()  # sigma_only: the colour head's input does not matter
+            with torch.no_grad():
+                rgb, sigma = ops.nerf_mlp(xyz, d, 1, self.packed("bf16"))
+            return sigma.unsqueeze(1) if sigma_only else torch.cat([rgb, sigma.unsqueeze(1)], 1)
         with torch.no_grad():
             rgb, sigma = nerf_points(self, xyz, None if input_dir is None else input_dir.contiguous().float(), 1, sigma_only=sigma_only)
         if sigma_only:

@@ -345,6 +345,64 @@ def points_along(rays, dir_col, z):
     return xyz
 
 
+# ----------------------------------------------------------------------------------- fused classic NeRF (csrc/nerf_fwd.inc)
+def nerf_fused_ok(model, mode):
+    """True when the one-launch classic-NeRF forward serves ``model`` in numeric mode ``mode``: single-pass bf16 at the shape of
+    models/__init__.py:8 (a width the library has a stream for, 8 layers, skip at 4, mapping sizes [10, 4])."""
+    return (mode == "bf16" and model.layers == 8 and list(model.skips) == [4] and list(model.mapping_sizes) == [10, 4]
+            and _lib.lib().sr_nerf_stream_elems(int(model.feat)) > 0)
+
+
+def nerf_render_ok(n_samples):
+    """True when sr_nerf_render_fwd takes ``n_samples`` samples per ray (a workgroup composites whole rays)."""
+    return 2 <= int(n_samples) <= _lib.lib().sr_nerf_render_max_samples()
+
+
+def _nerf_stream(stream, feat=256):
+    _chk(stream, "stream", torch.int16)
+    if stream.numel() != _lib.lib().sr_nerf_stream_elems(feat):
+        raise ValueError(f"stream holds {stream.numel()} elements, sr_nerf_stream_elems({feat}) = {_lib.lib().sr_nerf_stream_elems(feat)}")
+    return stream
+
+
+def nerf_mlp(xyz, dirs, row_div, stream):
+    """Fused classic ``NeRF.forward`` (models/nerf.py:184-227) in bf16: xyz (P,3) per point, dirs (rows,3) read at row p // row_div;
+    ``stream`` = ``NeRF.packed('bf16')``.  Returns rgb (P,3), sigma (P,)."""
+    xyz, sx = _rows(xyz, "xyz", 3)
+    dirs, sd = _rows(dirs, "dirs", 3)
+    p, row_div = xyz.shape[0], int(row_div)
+    if row_div < 1 or dirs.shape[0] * row_div < p:
+        raise ValueError(f"dirs has {dirs.shape[0]} rows x row_div {row_div} < {p} points")
+    _nerf_stream(stream)
+    rgb = torch.empty(p, 3, dtype=torch.float32, device=xyz.device)
+    sigma = torch.empty(p, dtype=torch.float32, device=xyz.device)
+    if p:
+        _lib.call("sr_nerf_mlp_fwd", _p(xyz), sx, _p(dirs), sd, row_div, p, 256, _p(stream), _p(rgb), _p(sigma), _stream())
+    return rgb, sigma
+
+
+def nerf_render_fwd(rays, n_samples, stream, u=None, z=None, noise=None, noise_std=0.0, want_z=False):
+    """One pass of the classic render in ONE launch (sr_nerf_render_fwd): depths (stratified from ``u`` (N,S), or ``z`` (N,S) as given)
+    -> points -> fused NeRF -> classic compositing (no sun, no sky, no clamp).  ``noise`` (N,S) is added to sigma times ``noise_std``.
+    Returns dict(rgb (N,3), depth (N,), weights, transparency (N,S), z (N,S) = the given ``z``, the depths drawn if ``want_z``, else None)."""
+    rays, stride = _rows(rays, "rays", 8)
+    n, s, dev = rays.shape[0], int(n_samples), rays.device
+    if (u is None) == (z is None):
+        raise ValueError("exactly one of u (stratified depths) and z (given depths) is required")
+    if not nerf_render_ok(s):
+        raise ValueError(f"n_samples={s} unsupported (2..{_lib.lib().sr_nerf_render_max_samples()})")
+    for t, nm in ((z, "z"), (u, "u"), (noise, "noise")):
+        if t is not None and tuple(_chk(t, nm).shape) != (n, s):
+            raise ValueError(f"{nm} must be ({n},{s}), got {tuple(t.shape)}")
+    _nerf_stream(stream)
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"rgb": e(n, 3), "depth": e(n), "weights": e(n, s), "transparency": e(n, s), "z": z if z is not None else (e(n, s) if want_z else None)}
+    if n:
+        _lib.call("sr_nerf_render_fwd", _p(rays), stride, n, s, _p(u), _p(z), _p(noise), float(noise_std), 256, _p(stream),
+                  _p(out["z"]) if z is None else None, _p(out["rgb"]), _p(out["depth"]), _p(out["weights"]), _p(out["transparency"]), _stream())
+    return out
+
+
 IMAGE_COLUMNS = {"rgb": (0, 3), "depth": (3, 4), "acc": (4, 5), "sun": (5, 6), "albedo": (6, 9), "beta": (9, 10), "sky": (10, 13)}
 
 

@@ -701,3 +701,92 @@ def pack_scatter_map(feat=256, tau=4):
     out = np.full((n, 2), -1, np.int32)
     out[params, rank] = words
     return out, scales
+
+
+# ------------------------------------------------------------------------------------------------ classic NeRF (csrc/nerf_fwd.inc)
+NERF_ENC_STEPS, NERF_DIR_STEPS = 4, 2  # aux k-steps: 60 encoded-xyz values + 1 | 24 encoded-direction values + 1
+NERF_ENC_ONE, NERF_DIR_ONE = 60, 24    # their constant-1 slots (biases)
+
+
+def nerf_param_shapes(feat=256, layers=8, skips=(4,), map_xyz=10, map_dir=4):
+    """Ordered ``{state_dict key: shape}`` of the classic ``NeRF`` (models/nerf.py:156-177, module registration order)."""
+    in_xyz, in_dir = 2 * map_xyz * 3, 2 * map_dir * 3
+    sh = OrderedDict()
+    for i in range(layers):
+        fan_in = in_xyz if i == 0 else (feat + in_xyz if i in skips else feat)
+        sh[f"fc_net.{2 * i}.weight"] = (feat, fan_in)
+        sh[f"fc_net.{2 * i}.bias"] = (feat,)
+    sh["sigma_from_xyz.0.weight"] = (1, feat)
+    sh["sigma_from_xyz.0.bias"] = (1,)
+    sh["feats_from_xyz.weight"] = (feat, feat)
+    sh["feats_from_xyz.bias"] = (feat,)
+    sh["rgb_from_xyzdir.0.weight"] = (feat // 2, feat + in_dir)
+    sh["rgb_from_xyzdir.0.bias"] = (feat // 2,)
+    sh["rgb_from_xyzdir.2.weight"] = (3, feat // 2)
+    sh["rgb_from_xyzdir.2.bias"] = (3,)
+    return sh
+
+
+def nerf_stages(feat=256):
+    """The stage list of NerfStream (csrc/nerf_fwd.inc) in consumption order: (name, output tiles, pieces per tile)."""
+    ks, hs, mt = feat // 16, feat // 32, feat // 32
+    trunk = [(f"fc_net.{2 * l}", mt, NERF_ENC_STEPS + ks if l == 4 else ks + 1) for l in range(1, 8)]
+    return [("fc_net.0", mt, NERF_ENC_STEPS)] + trunk + [("feats_from_xyz", mt, ks + 1), ("sigma_from_xyz.0", 1, ks + 1),
+                                                        ("rgb_from_xyzdir.0", mt // 2, ks + NERF_DIR_STEPS), ("rgb_from_xyzdir.2", 1, hs + 1)]
+
+
+@functools.lru_cache(maxsize=2)
+def nerf_forward_maps(feat=256):
+    """Gather maps of the fused classic-NeRF forward stream (mapping_sizes [10, 4], 8 layers, skip at 4): ``stream[i] =
+    bf16(flat[idx[i]])`` (idx < 0 -> 0), consumed by ``sr_pack_stream``.  Every stage's columns are [encoding k-steps | slot-permuted
+    activations | constant-1 k-step]: biases sit in the constant-1 slot of the encoded k-steps where a stage has them (fc_net.0,
+    fc_net.8: slot 60; rgb_from_xyzdir.0: slot 24 of the direction k-steps, which follow its activations) and in slot 0 of a k-step of
+    their own elsewhere.  Returns dict(idx int32 [n], scale fp32 [n], n_params, offsets)."""
+    if feat != 256:
+        raise ValueError(f"feat={feat}: the fused classic NeRF is built for width 256")
+    half, in_xyz, in_dir = feat // 2, 6 * 10, 6 * 4
+    offsets, n_params = param_offsets(nerf_param_shapes(feat))
+    enc = 16 * NERF_ENC_STEPS
+
+    def mat(rows, steps):
+        return _Mat(rows, 0, steps, offsets)  # k = 0: put_aux addresses absolute slots
+
+    mats = []
+    m = mat(feat, NERF_ENC_STEPS)
+    m.put_aux(0, "fc_net.0.weight", feat, 0, np.arange(in_xyz), 1.0)
+    m.put_aux(0, "fc_net.0.bias", feat, NERF_ENC_ONE, None, 1.0)
+    mats.append(m)
+    for l in range(1, 8):
+        name = f"fc_net.{2 * l}"
+        if l == 4:  # torch.cat([e, h]) (models/nerf.py:204): weight columns [enc (60) | h (feat)]
+            m = mat(feat, NERF_ENC_STEPS + feat // 16)
+            m.put_aux(0, name + ".weight", feat, 0, np.arange(in_xyz), 1.0)
+            m.put_aux(0, name + ".bias", feat, NERF_ENC_ONE, None, 1.0)
+            m.put_block(0, name + ".weight", feat, enc, feat, in_xyz, 1.0)
+        else:
+            m = mat(feat, feat // 16 + 1)
+            m.put_block(0, name + ".weight", feat, 0, feat, 0, 1.0)
+            m.put_aux(0, name + ".bias", feat, feat, None, 1.0)
+        mats.append(m)
+    m = mat(feat, feat // 16 + 1)
+    m.put_block(0, "feats_from_xyz.weight", feat, 0, feat, 0, 1.0)
+    m.put_aux(0, "feats_from_xyz.bias", feat, feat, None, 1.0)
+    mats.append(m)
+    m = mat(32, feat // 16 + 1)  # one tile whose row 0 is sigma
+    m.put_block(0, "sigma_from_xyz.0.weight", 1, 0, feat, 0, 1.0)
+    m.put_aux(0, "sigma_from_xyz.0.bias", 1, feat, None, 1.0)
+    mats.append(m)
+    m = mat(half, feat // 16 + NERF_DIR_STEPS)  # cat([feats, map(dir)]) (models/nerf.py:220)
+    m.put_block(0, "rgb_from_xyzdir.0.weight", half, 0, feat, 0, 1.0)
+    m.put_aux(0, "rgb_from_xyzdir.0.weight", half, feat, feat + np.arange(in_dir), 1.0)
+    m.put_aux(0, "rgb_from_xyzdir.0.bias", half, feat + NERF_DIR_ONE, None, 1.0)
+    mats.append(m)
+    m = mat(32, half // 16 + 1)  # rows 0..2: the colour logits
+    m.put_block(0, "rgb_from_xyzdir.2.weight", 3, 0, half, 0, 1.0)
+    m.put_aux(0, "rgb_from_xyzdir.2.bias", 3, half, None, 1.0)
+    mats.append(m)
+    assert [(m.idx.shape[0] // 32, m.idx.shape[1] // 16) for m in mats] == [(t, p) for _, t, p in nerf_stages(feat)]
+    parts = [_serialize(m) for m in mats]
+    idx = np.concatenate([p[0] for p in parts]).astype(np.int32)
+    scale = np.concatenate([p[1] for p in parts]).astype(np.float32)
+    return dict(idx=idx, scale=scale, n_params=n_params, offsets=offsets)

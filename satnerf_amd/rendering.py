@@ -300,8 +300,9 @@ def _render_rays_snerf(models, args, rays):
 
 
 def _render_rays_nerf(models, args, rays):
-    """``render_rays`` for the classic nerf (rendering.py:126-128,141-153; BASELINE configs[0]): rays are (N,8), no ts; every
-    layer runs through the MFMA GEMM of the layer-by-layer path and is differentiable when grad is enabled."""
+    """``render_rays`` for the classic nerf (rendering.py:126-128,141-153; BASELINE configs[0]): rays are (N,8), no ts.  Without grad
+    and in ``bf16`` each pass is one fused launch (csrc/nerf_fwd.inc); otherwise every layer runs through the MFMA GEMM of the
+    layer-by-layer path and is differentiable when grad is enabled."""
     from .generic import nerf_inference_pass
 
     if not rays.is_cuda:
@@ -310,6 +311,26 @@ def _render_rays_nerf(models, args, rays):
     n, dev, s = rays.shape[0], rays.device, args.n_samples
     grad = torch.is_grad_enabled() and any(p.requires_grad for p in models["coarse"].parameters())
     result = {}
+    mode = _mode_of(args)
+    fused = not grad and all(hasattr(models[t], "fused_forward") and models[t].fused_forward(mode) and ops.nerf_render_ok(k)
+                             for t, k in (("coarse", s), ("fine", s + args.n_importance))[:2 if args.n_importance > 0 else 1])
+    if fused:  # bf16 inference: each pass is one launch (sr_nerf_render_fwd); the draws keep the layer path's order and shapes
+        use_noise = float(args.noise_std) != 0
+        with torch.no_grad():
+            u, noise = _rng.rand(n, s, dev), _rng.randn(n, s, dev)
+            o = ops.nerf_render_fwd(rays, s, models["coarse"].packed(mode), u=u, noise=noise if use_noise else None, noise_std=float(args.noise_std),
+                                    want_z=args.n_importance > 0)
+            for k in ("rgb", "depth", "weights", "transparency"):
+                result[f"{k}_coarse"] = o[k]
+            if args.n_importance > 0:
+                u_fine = _rng.rand(n, args.n_importance, dev)
+                z_fine = ops.sample_pdf_merge(o["z"], o["weights"], u_fine) if n else torch.empty(0, s + args.n_importance, device=dev)
+                noise = _rng.randn(n, z_fine.shape[1], dev)
+                o = ops.nerf_render_fwd(rays, z_fine.shape[1], models["fine"].packed(mode), z=z_fine, noise=noise if use_noise else None,
+                                        noise_std=float(args.noise_std))
+                for k in ("rgb", "depth", "weights", "transparency"):
+                    result[f"{k}_fine"] = o[k]
+        return result
     with contextlib.nullcontext() if grad else torch.no_grad():
         z = ops.ray_sample(rays, _rng.rand(n, s, dev), s)
         for k, v in nerf_inference_pass(models["coarse"], args, rays, z, _rng.randn(n, s, dev)).items():
