@@ -18,6 +18,17 @@ long fwd512_stream_pieces_a1();
 long fwd512_stream_pieces_a2();
 }  // namespace sr
 using namespace sr;
+
+// (feat, mode, aux size) -> the translation unit's entry; the callers have checked that the combination exists
+using FwdLaunch = int (*)(const FwdParams&, int, hipStream_t);
+static FwdLaunch fwd_launcher(int feat, int mode, int auxs) {
+  if (feat == 512 && mode == SR_MODE_F16) return auxs == 1 ? launch_fwd512_h1a1 : launch_fwd512_h1a2;
+  if (feat == 512) return auxs == 1 ? launch_fwd512_p1a1 : launch_fwd512_p1a2;
+  if (mode == SR_MODE_BF16) return auxs == 1 ? launch_fwd_p1a1 : launch_fwd_p1a2;
+  if (mode == SR_MODE_F16) return auxs == 1 ? launch_fwd_h1a1 : launch_fwd_h1a2;
+  return auxs == 1 ? launch_fwd_p3a1 : launch_fwd_p3a2;
+}
+
 extern "C" int sr_satnerf_mlp_fwd(const sr_mlp_inputs* in, int feat, int tau, int mode, const uint16_t* stream_hi,
                                   const uint16_t* stream_lo, const float* l0, float* albedo, float* sigma, float* sun_v,
                                   float* beta, uint16_t* acts, int act_fmt, void* stream) {
@@ -42,14 +53,7 @@ extern "C" int sr_satnerf_mlp_fwd(const sr_mlp_inputs* in, int feat, int tau, in
   p.albedo = albedo, p.sigma = sigma, p.sun_v = sun_v, p.beta = beta;
   p.acts = (uint4*)acts;
   p.tau = tau;
-  hipStream_t st = (hipStream_t)stream;
-  const int save = acts != nullptr ? act_fmt : 0;
-  const int auxs = aux_steps(tau);
-  if (feat == 512 && mode == SR_MODE_F16) return auxs == 1 ? launch_fwd512_h1a1(p, save, st) : launch_fwd512_h1a2(p, save, st);
-  if (feat == 512) return auxs == 1 ? launch_fwd512_p1a1(p, save, st) : launch_fwd512_p1a2(p, save, st);
-  if (mode == SR_MODE_BF16) return auxs == 1 ? launch_fwd_p1a1(p, save, st) : launch_fwd_p1a2(p, save, st);
-  if (mode == SR_MODE_F16) return auxs == 1 ? launch_fwd_h1a1(p, save, st) : launch_fwd_h1a2(p, save, st);
-  return auxs == 1 ? launch_fwd_p3a1(p, save, st) : launch_fwd_p3a2(p, save, st);
+  return fwd_launcher(feat, mode, aux_steps(tau))(p, acts != nullptr ? act_fmt : 0, (hipStream_t)stream);
 }
 
 extern "C" int64_t sr_fwd_stream_elems(int feat, int tau) {
@@ -60,8 +64,8 @@ extern "C" int64_t sr_fwd_stream_elems(int feat, int tau) {
 
 extern "C" int sr_render_points_per_block(int feat, int mode) {
   if (mode != SR_MODE_BF16 && mode != SR_MODE_BF16X3 && mode != SR_MODE_F16) return -1;
-  if (feat == kFeat) return mode == SR_MODE_BF16X3 ? 128 : 256;  // Mode<NPASS>::NW * 32
-  if (feat == 512 && (mode == SR_MODE_BF16 || mode == SR_MODE_F16)) return 128;
+  if (feat == kFeat) return (mode == SR_MODE_BF16X3 ? kFwdWavesParity : kFwdWaves256) * 32;  // a wave = one 32-point tile
+  if (feat == 512 && (mode == SR_MODE_BF16 || mode == SR_MODE_F16)) return kFwdWaves512 * 32;
   return -1;
 }
 
@@ -119,14 +123,7 @@ static int render_launch(const char* who, const sr_render_args* in, int feat, in
   p.stream_hi = (const char*)stream_hi, p.stream_lo = (const char*)stream_lo, p.l0 = (const float4*)l0;
   p.albedo = out->albedo, p.sigma = out->sigma, p.sun_v = out->sun_v, p.beta = out->beta;
   p.acts = (uint4*)acts, p.tau = tau;
-  hipStream_t st = (hipStream_t)stream;
-  const int save = acts != nullptr ? act_fmt : 0;
-  const int auxs = aux_steps(tau);
-  if (feat == 512 && mode == SR_MODE_F16) return auxs == 1 ? launch_fwd512_h1a1(p, save, st) : launch_fwd512_h1a2(p, save, st);
-  if (feat == 512) return auxs == 1 ? launch_fwd512_p1a1(p, save, st) : launch_fwd512_p1a2(p, save, st);
-  if (mode == SR_MODE_BF16) return auxs == 1 ? launch_fwd_p1a1(p, save, st) : launch_fwd_p1a2(p, save, st);
-  if (mode == SR_MODE_F16) return auxs == 1 ? launch_fwd_h1a1(p, save, st) : launch_fwd_h1a2(p, save, st);
-  return auxs == 1 ? launch_fwd_p3a1(p, save, st) : launch_fwd_p3a2(p, save, st);
+  return fwd_launcher(feat, mode, aux_steps(tau))(p, acts != nullptr ? act_fmt : 0, (hipStream_t)stream);
 }
 
 extern "C" int sr_satnerf_render_fwd(const sr_render_args* in, int feat, int tau, int mode, const uint16_t* stream_hi, const uint16_t* stream_lo,

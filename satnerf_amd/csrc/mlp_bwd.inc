@@ -546,9 +546,6 @@ __global__ void __launch_bounds__(Mode<1>::NW * 64) satnerf_bwd_kernel(const Bwd
       xq[i / 8][4 * (i % 8)] = f.x, xq[i / 8][4 * (i % 8) + 1] = f.y, xq[i / 8][4 * (i % 8) + 2] = f.z, xq[i / 8][4 * (i % 8) + 3] = f.w;
     }
     if constexpr (kStreamG1) xs = u32x4w{d_g1[0][kKS].x, d_g1[0][kKS].y, d_g1[0][kKS].z, d_g1[0][kKS].w};
-    auto uni64 = [](uint64_t v) {
-      return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    };
     const uint32_t ring_addr = lds_addr_of(ring);
     const uint32_t vl0 = ring_addr + (uint32_t)lane * 16u, vl1 = vl0 + 65536u;
     uint32_t voff = (uint32_t)wave * 1024u + (uint32_t)lane * 16u;
@@ -556,7 +553,7 @@ __global__ void __launch_bounds__(Mode<1>::NW * 64) satnerf_bwd_kernel(const Bwd
     uint32_t soff = (uint32_t)((unsigned long)tile0 * DK * 1024ul) + (uint32_t)lane * 16u;
     const uint32_t vcell = lds_addr_of(reinterpret_cast<const char*>(emax[0]));
     const uint32_t wb = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ring_addr + (uint32_t)wave * 1024u));
-    const uint64_t sb = uni64((uint64_t)(uintptr_t)(stream + (kStreamG1 ? BS::offset_pieces(BS::G_G1) : offL) * 1024L)), ab = uni64((uint64_t)(uintptr_t)prm.acts), db = uni64((uint64_t)(uintptr_t)prm.dpre);
+    const uint64_t sb = uniform64(stream + (kStreamG1 ? BS::offset_pieces(BS::G_G1) : offL) * 1024L), ab = uniform64(prm.acts), db = uniform64(prm.dpre);
     const float magic = 12583040.0f;  // 1.5 * 2^23 + 128 (codec8.h mx8_encode)
     const uint32_t k43 = 0x43000000u;
     uint32_t m0save;

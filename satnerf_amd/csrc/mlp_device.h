@@ -59,12 +59,16 @@ __device__ __forceinline__ void glds16(const char* gsrc, uint32_t lds_addr) {
       : "v"(gsrc), "s"(lds_addr)
       : "memory");
 }
+// a wave-uniform 64-bit pointer as an SGPR pair: the two readfirstlanes tell the compiler that the value is uniform (they fold away
+// when it already is)
+__device__ __forceinline__ uint64_t uniform64(const void* p) {
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
 // the same with the address split into a wave-uniform 64-bit base (SGPR pair: advanced by scalar adds, no VALU address
 // arithmetic per piece) and a 32-bit per-lane byte offset
 __device__ __forceinline__ void glds16_s(const char* sbase, uint32_t voff, uint32_t lds_addr) {
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;  // readfirstlane: tells the compiler the base is uniform (folds away when it already is)
-  const uint64_t ub = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+  const uint64_t ub = uniform64(sbase);
   uint32_t keep;
   asm volatile(
       "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -76,9 +80,7 @@ __device__ __forceinline__ void glds16_s(const char* sbase, uint32_t voff, uint3
 // increment) instead of being branched around -- a branch per potential request costs the in-order wave more than the
 // dead issue slot
 __device__ __forceinline__ void glds16_s_if(bool on, const char* sbase, uint32_t voff, uint32_t lds_addr) {
-  const uint64_t b = (uint64_t)(uintptr_t)sbase;
-  const uint64_t ub = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+  const uint64_t ub = uniform64(sbase);
   const uint32_t pred = __builtin_amdgcn_readfirstlane((int)on);
   uint32_t keep;
   uint64_t ex;

@@ -310,10 +310,16 @@ __device__ __forceinline__ PointIn point_setup(const FwdParams& prm, float* r_z,
 
 }
 
+// the workspace copy of one aux fragment: bf16 whatever the forward's single-pass operand format, it is an operand of the (bf16) backward kernels
+__device__ __forceinline__ uint4 aux_ws_bf16(const float (&v)[8]) {
+  return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+}
+
 template <int NPASS, int AUXS, int SAVE, int KG, bool REND = false>
 __global__ void __launch_bounds__(Mode<NPASS>::NW * 64) satnerf_fwd_kernel(const FwdParams prm) {
   using FS = FwdStream<AUXS>;
   constexpr int NW = Mode<NPASS>::NW;
+  static_assert(NW == (kFeat != 256 ? kFwdWaves512 : NPASS == 1 ? kFwdWaves256 : kFwdWavesParity), "sr_render_points_per_block (mlp_params.h)");
   constexpr int SLOT_BYTES = FS::SLOTP * Mode<NPASS>::PIECE_BYTES;
   constexpr int AK = SAVE == SR_FMT8 ? act8_units(AUXS) : act_ksteps(AUXS);  // workspace units per tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -349,7 +355,7 @@ __global__ void __launch_bounds__(Mode<NPASS>::NW * 64) satnerf_fwd_kernel(const
   uint4 aux_ws[AUXS];
 #endif
   {
-    float av[AUXS][8];
+    float av[AUXS][8];  // mlp_fwd_io.inc aux_values' fill, spelled out: hipcc schedules this kernel end to end, and calling the helper moved its instruction count (-11 .. +13)
 #pragma unroll
     for (int a = 0; a < AUXS; ++a)
 #pragma unroll
@@ -371,8 +377,7 @@ __global__ void __launch_bounds__(Mode<NPASS>::NW * 64) satnerf_fwd_kernel(const
       aux.hi[a] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
       if constexpr (NPASS == 3) aux.lo[a] = make_uint4(lw[0], lw[1], lw[2], lw[3]);
 #ifdef SR_F16  // the workspace copy of the aux fragment is an operand of the (bf16) backward kernels
-      aux_ws[a] = make_uint4(pack_bf16x2(av[a][0], av[a][1]), pack_bf16x2(av[a][2], av[a][3]), pack_bf16x2(av[a][4], av[a][5]),
-                             pack_bf16x2(av[a][6], av[a][7]));
+      aux_ws[a] = aux_ws_bf16(av[a]);
 #endif
     }
   }
@@ -550,24 +555,29 @@ __global__ void __launch_bounds__(Mode<NPASS>::NW * 64) satnerf_fwd_kernel(const
 
 namespace sr {
 inline namespace SR_FEAT_NS {
+// The launch of every forward kernel of this family (this file's and the generated-core ones): workgroups of `nw` waves, one 32-point
+// tile per wave; dynamic LDS = the kernel's own `lds_bytes` (ring, fc_net.0 table) + `rend_floats` floats per point of the workgroup
+// for the render epilogue (0 = a plain MLP launch; a render launch composites whole rays, so n_samples must divide the workgroup).
+using FwdKernel = void (*)(const FwdParams);
+inline int launch_fwd_kernel(FwdKernel kern, const char* name, int nw, size_t lds_bytes, int rend_floats, const FwdParams& p, hipStream_t st) {
+  const size_t lds = lds_bytes + (size_t)nw * 32 * rend_floats * sizeof(float);
+  if (rend_floats != 0 && (nw * 32) % p.in.n_samples != 0) {
+    set_error("sr_satnerf_render_fwd: n_samples=%d must divide the %d points of a workgroup (sr_render_points_per_block)", p.in.n_samples, nw * 32);
+    return 1;
+  }
+  const long tiles = (p.in.n_points + 31) / 32;
+  const unsigned grid = (unsigned)((tiles + nw - 1) / nw);
+  if (!ensure_dynamic_lds((const void*)kern, lds)) return 1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, st, p);
+  return check_launch(name);
+}
+
 template <int NPASS, int AUXS, int SAVE, int KG, bool REND = false>
 int launch_one(const FwdParams& p, hipStream_t st) {
   using FS = FwdStream<AUXS>;
-  constexpr int NW = Mode<NPASS>::NW;
   static_assert(FS::N_TRUNK % (2 * KG) == 0 && FS::NCH % KG == 0 && kMT % KG == 0, "chunk groups must tile the stream and the ring");
-  const size_t lds = (size_t)ring_slots<KG>() * FS::SLOTP * Mode<NPASS>::PIECE_BYTES + kFeat * sizeof(float4) + (REND ? NW * 32 * 6 * sizeof(float) : 0);
-  if constexpr (REND) {
-    if ((NW * 32) % p.in.n_samples != 0) {
-      set_error("sr_satnerf_render_fwd: n_samples=%d must divide the %d points of a workgroup (sr_render_points_per_block)", p.in.n_samples, NW * 32);
-      return 1;
-    }
-  }
-  const long tiles = (p.in.n_points + 31) / 32;
-  const unsigned grid = (unsigned)((tiles + NW - 1) / NW);
-  auto kern = satnerf_fwd_kernel<NPASS, AUXS, SAVE, KG, REND>;
-  if (!ensure_dynamic_lds((const void*)kern, lds)) return 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, p);
-  return check_launch("satnerf_fwd_kernel");
+  const size_t ring = (size_t)ring_slots<KG>() * FS::SLOTP * Mode<NPASS>::PIECE_BYTES + kFeat * sizeof(float4);
+  return launch_fwd_kernel(satnerf_fwd_kernel<NPASS, AUXS, SAVE, KG, REND>, "satnerf_fwd_kernel", Mode<NPASS>::NW, ring, REND ? 6 : 0, p, st);  // 6: no beta in LDS
 }
 
 #ifndef SR_FWD_GROUP

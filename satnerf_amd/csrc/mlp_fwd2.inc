@@ -49,7 +49,7 @@ __device__ __forceinline__ void split3(float v, float& h, float& m, float& l) {
 // encoding and the non-temporal stores are part of the generated stream)
 template <int AUXS, bool REND, int SAVE = 0>
 __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) {
-  constexpr int NW = 8;
+  constexpr int NW = kFwdWaves256;  // (gen/fwd_core.py feeds the ring in rows of 8)
   constexpr int AK = act8_units(AUXS);  // workspace units per tile (SAVE)
   static_assert(SAVE == 0 || SAVE == SR_FMT8, "the generated core saves in the 8-bit format only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -86,30 +86,17 @@ __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) 
   const PointIn in = point_setup<REND, NW>(prm, r_z, wave, lane);
   const long tile = in.tile;
   const float x = in.x, y = in.y, zc = in.zc;
-  const float *sn = in.sn, *te = in.te;
 
-  // aux fragment(s): slots [sun(3), 1, xyz(3), 0 | t(0..7) | t(8..15) | t(16..23)]
+  // aux fragment(s) in the operand format, and their workspace copy (mlp_fwd_io.inc aux_values: the slots)
   uint4 auxf[AUXS];
   uint4* save = SAVE ? prm.acts + (tile * AK) * 64 + lane : nullptr;
   {
     float av[AUXS][8];
-#pragma unroll
-    for (int a = 0; a < AUXS; ++a)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int q = 16 * a + 8 * h + j;
-        float val = 0.f;
-        if (q >= 8) { const int ti = q - 8; val = ti < prm.tau ? te[ti < prm.tau ? ti : 0] : 0.f; }
-        av[a][j] = val;
-      }
-    if (h == 0) { av[0][0] = sn[0], av[0][1] = sn[1], av[0][2] = sn[2], av[0][3] = 1.f, av[0][4] = x, av[0][5] = y, av[0][6] = zc, av[0][7] = 0.f; }
+    aux_values<AUXS>(prm, in, lane, av);
 #pragma unroll
     for (int a = 0; a < AUXS; ++a) {
       auxf[a] = make_uint4(pack_op2(av[a][0], av[a][1]), pack_op2(av[a][2], av[a][3]), pack_op2(av[a][4], av[a][5]), pack_op2(av[a][6], av[a][7]));
-      if constexpr (SAVE != 0) {  // the workspace copy is an operand of the (bf16) backward kernels, whatever the forward's operand format
-        ws_store(save + a * 64, make_uint4(pack_bf16x2(av[a][0], av[a][1]), pack_bf16x2(av[a][2], av[a][3]), pack_bf16x2(av[a][4], av[a][5]),
-                                           pack_bf16x2(av[a][6], av[a][7])));
-      }
+      if constexpr (SAVE != 0) ws_store(save + a * 64, aux_ws_bf16(av[a]));
     }
   }
 
@@ -136,9 +123,7 @@ __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) 
   const uint32_t vl0 = ring_addr + (uint32_t)lane * 16u, vl1 = vl0 + 65536u;
   uint32_t voff = (uint32_t)wave * 1024u + (uint32_t)lane * 16u;
   const uint32_t wb = __builtin_amdgcn_readfirstlane(ring_addr + (uint32_t)wave * 1024u);
-  const uint64_t sb64 = (uint64_t)(uintptr_t)prm.stream_hi;  // ring piece p is stream piece p - 16: the first requested row is row 2, at source offset 0
-  const uint64_t sb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sb64 >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sb64);
+  const uint64_t sb = uniform64(prm.stream_hi);  // ring piece p is stream piece p - 16: the first requested row is row 2, at source offset 0
   f32x16 acc;
   float sig;
   uint32_t m0save;
@@ -149,9 +134,7 @@ __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) 
   // SAVE: this lane's workspace offset (tile base + lane * 16; the stream advances it unit by unit) and the PHASE8 constant
   uint32_t soff = (uint32_t)((unsigned long)tile * AK * 1024ul) + (uint32_t)lane * 16u;
   const float kmagic = 49152.0f, k128 = 128.0f;
-  const uint64_t ab64 = (uint64_t)(uintptr_t)prm.acts;
-  const uint64_t ab = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ab64 >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ab64);
+  const uint64_t ab = uniform64(prm.acts);
 #define SR_CORE_OUTS "={v[192:207]}"(acc), "={v208}"(sig), "+{v211}"(voff), [m0save] "=&s"(m0save)
 #define SR_CORE_INS "{v[232:235]}"(l0b0), "{v[236:239]}"(l0b1), "{v209}"(vl0), "{v210}"(vl1), [sb] "s"(sb), [wb] "s"(wb), [wave] "s"(wave)
   if constexpr (AUXS == 1 && SAVE == 0) {
@@ -197,51 +180,23 @@ __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) 
 #undef SR_CORE_INS
 
 #ifdef SR_CORE_TIMING
-  {
-    const uint64_t t_core1 = __builtin_amdgcn_s_memtime();
-    const uint64_t r_core1 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0 && prm.sigma && prm.sun_v) {
-      prm.sigma[tile] = (float)(t_core1 - t_core0);
-      prm.sun_v[tile] = (float)(t_core0 - t_kernel0);
-      if (prm.beta) prm.beta[tile] = (float)(r_core1 - r_core0);  // constant 100 MHz ticks
-    }
-    return;
-  }
+  core_timing_store(prm, tile, lane, t_kernel0, t_core0, r_core0);
+  return;
 #endif
   write_outputs<REND, NW>(prm, in, acc, sig, r_z, wave, lane);
 }
 
 template <int AUXS, bool REND, int SAVE = 0>
 int launch_fwd2(const FwdParams& p, hipStream_t st) {
-  constexpr int NW = 8;
-  const size_t lds = (size_t)kRing2 * 1024 + (REND ? NW * 32 * kRendFloats * sizeof(float) : 0);
-  if constexpr (REND) {
-    if ((NW * 32) % p.in.n_samples != 0) {
-      set_error("sr_satnerf_render_fwd: n_samples=%d must divide the %d points of a workgroup (sr_render_points_per_block)", p.in.n_samples, NW * 32);
-      return 1;
-    }
-  }
-  const long tiles = (p.in.n_points + 31) / 32;
-  const unsigned grid = (unsigned)((tiles + NW - 1) / NW);
-  auto kern = satnerf_fwd2_kernel<AUXS, REND, SAVE>;
-  if (!ensure_dynamic_lds((const void*)kern, lds)) return 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, p);
-  return check_launch("satnerf_fwd2_kernel");
+  return launch_fwd_kernel(satnerf_fwd2_kernel<AUXS, REND, SAVE>, "satnerf_fwd2_kernel", kFwdWaves256, (size_t)kRing2 * 1024, REND ? kRendFloats : 0, p, st);
 }
 
 // entry of the (1, AUXS) translation units: the generated core for inference and for the 8-bit training forward, unless
-// SATNERF_FWD_V1=1 selects the r02 kernels (A/B); 16-bit workspaces stay on mlp_fwd.inc
+// SATNERF_FWD_V1=1 selects the r02 kernels (A/B); 16-bit workspaces stay on mlp_fwd.inc (mlp_fwd_io.inc fwd_route)
 template <int AUXS>
 int launch_fwd_any(const FwdParams& p, int save_fmt, hipStream_t st) {
-  static const bool v1 = [] { const char* e = getenv("SATNERF_FWD_V1"); return e && e[0] == '1'; }();
-  const unsigned long ws_bytes = (unsigned long)ws_tiles(p.in.n_points) * act8_units(AUXS) * 1024ul;  // 32-bit offsets in the stream (tail waves included)
-  if (v1 || (save_fmt != 0 && save_fmt != SR_FMT8) || (save_fmt == SR_FMT8 && ws_bytes >= (1ul << 32))) {
-    if (p.train.target != nullptr) {
-      set_error("sr_satnerf_render_train: no fused training forward for this configuration (SATNERF_FWD_V1, a 16-bit workspace or >= 4 GiB of it): use the separate launches");
-      return 1;
-    }
-    return launch_fwd<1, AUXS>(p, save_fmt, st);
-  }
+  const FwdRoute route = fwd_route(p, save_fmt, SR_FMT8, act8_units(AUXS), true);
+  if (route != FwdRoute::Core) return route == FwdRoute::Refused ? 1 : launch_fwd<1, AUXS>(p, save_fmt, st);
   if (save_fmt == SR_FMT8) return p.rend.rays != nullptr ? launch_fwd2<AUXS, true, SR_FMT8>(p, st) : launch_fwd2<AUXS, false, SR_FMT8>(p, st);
   return p.rend.rays != nullptr ? launch_fwd2<AUXS, true>(p, st) : launch_fwd2<AUXS, false>(p, st);
 }

@@ -34,7 +34,7 @@ __device__ __forceinline__ u32x32_3 cat8(const uint4* f) {
 
 template <int AUXS, bool REND, int SAVE = 0>
 __global__ void __launch_bounds__(256) satnerf_fwd3_kernel(const FwdParams prm) {
-  constexpr int NW = 4;
+  constexpr int NW = kFwdWavesParity;  // (gen/fwd_core3.py feeds the ring in rows of 4)
   constexpr int AK = act_ksteps(AUXS);  // workspace fragments per tile (SAVE)
   static_assert(SAVE == 0 || SAVE == SR_FMT16, "the parity mode saves 16-bit workspaces");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -55,22 +55,12 @@ __global__ void __launch_bounds__(256) satnerf_fwd3_kernel(const FwdParams prm) 
   const PointIn in = point_setup<REND, NW>(prm, r_z, wave, lane);
   const long tile = in.tile;
   const float x = in.x, y = in.y, zc = in.zc;
-  const float *sn = in.sn, *te = in.te;
 
-  // aux fragment(s), hi and lo planes: slots [sun(3), 1, xyz(3), 0 | t(0..7) | t(8..15) | t(16..23)]
+  // aux fragment(s), hi and lo planes (mlp_fwd_io.inc aux_values: the slots)
   u32x16_3 auxv = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // [hi a0, hi a1, lo a0, lo a1]
   {
     float av[AUXS][8];
-#pragma unroll
-    for (int a = 0; a < AUXS; ++a)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int q = 16 * a + 8 * h + j;
-        float val = 0.f;
-        if (q >= 8) { const int ti = q - 8; val = ti < prm.tau ? te[ti < prm.tau ? ti : 0] : 0.f; }
-        av[a][j] = val;
-      }
-    if (h == 0) { av[0][0] = sn[0], av[0][1] = sn[1], av[0][2] = sn[2], av[0][3] = 1.f, av[0][4] = x, av[0][5] = y, av[0][6] = zc, av[0][7] = 0.f; }
+    aux_values<AUXS>(prm, in, lane, av);
 #pragma unroll
     for (int a = 0; a < AUXS; ++a)
 #pragma unroll
@@ -108,10 +98,6 @@ __global__ void __launch_bounds__(256) satnerf_fwd3_kernel(const FwdParams prm) 
   const uint32_t vl0 = ring_addr + (uint32_t)lane * 16u, vl1 = vl0 + 65536u;
   uint32_t voff = (uint32_t)wave * 1024u + (uint32_t)lane * 16u;
   const uint32_t wb = __builtin_amdgcn_readfirstlane(ring_addr + (uint32_t)wave * 2048u);
-  auto uniform64 = [](const void* p) {
-    const uint64_t v = (uint64_t)(uintptr_t)p;
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  };
   const uint64_t sh = uniform64(prm.stream_hi), sl = uniform64(prm.stream_lo);
   f32x16 acc;
   float sig;
@@ -164,45 +150,25 @@ __global__ void __launch_bounds__(256) satnerf_fwd3_kernel(const FwdParams prm) 
 #undef SR_CORE3_INS
 
 #ifdef SR_CORE_TIMING
-  {
-    const uint64_t t_core1 = __builtin_amdgcn_s_memtime();
-    const uint64_t r_core1 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0 && prm.sigma && prm.sun_v) {
-      prm.sigma[tile] = (float)(t_core1 - t_core0);
-      prm.sun_v[tile] = (float)(t_core0 - t_kernel0);
-      if (prm.beta) prm.beta[tile] = (float)(r_core1 - r_core0);  // constant 100 MHz ticks
-    }
-    return;
-  }
+  core_timing_store(prm, tile, lane, t_kernel0, t_core0, r_core0);
+  return;
 #endif
   write_outputs<REND, NW>(prm, in, acc, sig, r_z, wave, lane);
 }
 
 template <int AUXS, bool REND, int SAVE = 0>
 int launch_fwd3(const FwdParams& p, hipStream_t st) {
-  constexpr int NW = 4;
-  const size_t lds = (size_t)kRing3 * 2048 + kFeat * sizeof(float4) + (REND ? NW * 32 * kRendFloats * sizeof(float) : 0);
-  if constexpr (REND) {
-    if ((NW * 32) % p.in.n_samples != 0) {
-      set_error("sr_satnerf_render_fwd: n_samples=%d must divide the %d points of a workgroup (sr_render_points_per_block)", p.in.n_samples, NW * 32);
-      return 1;
-    }
-  }
-  const long tiles = (p.in.n_points + 31) / 32;
-  const unsigned grid = (unsigned)((tiles + NW - 1) / NW);
-  auto kern = satnerf_fwd3_kernel<AUXS, REND, SAVE>;
-  if (!ensure_dynamic_lds((const void*)kern, lds)) return 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, p);
-  return check_launch("satnerf_fwd3_kernel");
+  return launch_fwd_kernel(satnerf_fwd3_kernel<AUXS, REND, SAVE>, "satnerf_fwd3_kernel", kFwdWavesParity, (size_t)kRing3 * 2048 + kFeat * sizeof(float4),
+                           REND ? kRendFloats : 0, p, st);
 }
 
 // entry of the (3, AUXS) translation units: the generated core for inference, the render pass and the 16-bit training forward unless
-// SATNERF_FWD_V1=1 selects the hipcc-scheduled kernel (A/B; it also keeps what the stream's 32-bit workspace offsets cannot address)
+// SATNERF_FWD_V1=1 selects the hipcc-scheduled kernel (A/B; it also keeps what the stream's 32-bit workspace offsets cannot address,
+// and a render launch with a workspace: mlp_fwd_io.inc fwd_route)
 template <int AUXS>
 int launch_fwd3_any(const FwdParams& p, int save_fmt, hipStream_t st) {
-  static const bool v1 = [] { const char* e = getenv("SATNERF_FWD_V1"); return e && e[0] == '1'; }();
-  const unsigned long ws_bytes = (unsigned long)ws_tiles(p.in.n_points) * act_ksteps(AUXS) * 1024ul;
-  if (v1 || (save_fmt != 0 && (save_fmt != SR_FMT16 || p.rend.rays != nullptr || ws_bytes >= (1ul << 32)))) return launch_fwd<3, AUXS>(p, save_fmt, st);
+  const FwdRoute route = fwd_route(p, save_fmt, SR_FMT16, act_ksteps(AUXS), false);
+  if (route != FwdRoute::Core) return route == FwdRoute::Refused ? 1 : launch_fwd<3, AUXS>(p, save_fmt, st);
   if (save_fmt == SR_FMT16) return launch_fwd3<AUXS, false, SR_FMT16>(p, st);
   return p.rend.rays != nullptr ? launch_fwd3<AUXS, true>(p, st) : launch_fwd3<AUXS, false>(p, st);
 }

@@ -1,11 +1,86 @@
-// What the generated-core forward kernels (mlp_fwd2.inc, mlp_fwd3.inc, mlp_fwd512g.inc) share behind their instruction streams: the output
-// activations / the one-launch render epilogue (the set-up of a lane's sample point, point_setup, is in mlp_fwd.inc: every forward kernel
-// uses it).  NW = waves per workgroup (a workgroup's NW * 32 consecutive points are whole rays under REND).
+// The shell of the generated-core forward kernels (mlp_fwd2.inc, mlp_fwd3.inc, mlp_fwd512g.inc), everything around their instruction
+// streams that is not a kernel's own geometry:
+//   aux_values         the fp32 slot values of a lane's aux fragment(s), in front of the stream
+//   write_outputs      the output activations / the one-launch render and training epilogue behind the stream
+//   core_timing_store  the SR_CORE_TIMING experiment's three floats
+//   fwd_route          host: generated core, compiler-scheduled kernel (mlp_fwd.inc) or error, for the three launch_fwd*_any
+// The rest of the shell is in mlp_fwd.inc, beside the compiler-scheduled kernel that shares it (point_setup, aux_ws_bf16,
+// launch_fwd_kernel), and in mlp_device.h (uniform64).  NW = waves per workgroup (a workgroup's NW * 32 consecutive points are whole
+// rays under REND).
 #pragma once
+#include <stdlib.h>
+
 #include "mlp_fwd.inc"
 
 namespace sr {
+
+// SATNERF_FWD_V1=1: every forward launch of the process runs the compiler-scheduled kernel (A/B against the generated cores)
+inline bool fwd_v1_forced() {
+  static const bool v1 = [] { const char* e = getenv("SATNERF_FWD_V1"); return e && e[0] == '1'; }();
+  return v1;
+}
+
+// Where a forward launch runs.  The generated core takes inference and its one native save format, while the stream's 32-bit workspace
+// offsets reach the whole workspace (tail waves included); everything else is the compiler-scheduled kernel's, which has no training
+// epilogue.  Today's callers (native format, units per tile, may a render launch save):
+//   launch_fwd_any     256, bf16 / f16   SR_FMT8    act8_units   yes (the one-launch training forward)
+//   launch_fwd3_any    256, parity       SR_FMT16   act_ksteps   no  (falls back; launch_fwd refuses a render launch that saves)
+//   launch_fwd512_any  512, bf16 / f16   SR_FMT8    act8_units   yes
+//   save_fmt   render launch   workspace   SATNERF_FWD_V1 | route
+//   0          any             -           unset          | Core
+//   native     no              < 4 GiB     unset          | Core
+//   native     yes             < 4 GiB     unset          | Core if a render launch may save, else Scheduled
+//   native     any             >= 4 GiB    unset          | Scheduled
+//   other      any             any         unset          | Scheduled
+//   any        any             any         1              | Scheduled
+//   ... and Scheduled with train.target set                | Refused (error set; the parity mode has no training launch, mlp_api.hip)
+enum class FwdRoute { Core, Scheduled, Refused };
+inline FwdRoute fwd_route(const FwdParams& p, int save_fmt, int native_fmt, int units_per_tile, bool rend_may_save) {
+  const unsigned long ws_bytes = (unsigned long)ws_tiles(p.in.n_points) * units_per_tile * 1024ul;
+  const bool rend = p.rend.rays != nullptr;
+  if (!fwd_v1_forced() && (save_fmt == 0 || (save_fmt == native_fmt && (rend_may_save || !rend) && ws_bytes < (1ul << 32)))) return FwdRoute::Core;
+  if (p.train.target != nullptr) {
+    set_error("sr_satnerf_render_train: no fused training forward for this configuration (SATNERF_FWD_V1, a 16-bit workspace or >= 4 GiB of it): use the separate launches");
+    return FwdRoute::Refused;
+  }
+  return FwdRoute::Scheduled;
+}
+
 inline namespace SR_FEAT_NS {
+
+// this lane's fp32 values of the aux fragment(s): slots [sun(3), 1, xyz(3), 0 | t(0..7) | t(8..15) | t(16..23)], av[a][j] = slot
+// 16 a + 8 h + j.  The shells pack their operand formats from these (tests/test_hip_fwd_reference.py pins the layout).
+// h is derived here, with its range stated: handed in as a plain int the helper is simplified before it is inlined without knowing
+// that h is 0 or 1, and the callers' fc_net.0 table reads behind it then came out with one address add each (+128..256 instructions).
+template <int AUXS>
+__device__ __forceinline__ void aux_values(const FwdParams& prm, const PointIn& in, int lane, float (&av)[AUXS][8]) {
+  const int h = lane >> 5;
+  __builtin_assume(h == 0 || h == 1);
+  const float *sn = in.sn, *te = in.te;
+  const float x = in.x, y = in.y, zc = in.zc;
+#pragma unroll
+  for (int a = 0; a < AUXS; ++a)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int q = 16 * a + 8 * h + j;  // aux slot
+      float val = 0.f;
+      if (q >= 8) { const int ti = q - 8; val = ti < prm.tau ? te[ti < prm.tau ? ti : 0] : 0.f; }
+      av[a][j] = val;
+    }
+  if (h == 0) { av[0][0] = sn[0], av[0][1] = sn[1], av[0][2] = sn[2], av[0][3] = 1.f, av[0][4] = x, av[0][5] = y, av[0][6] = zc, av[0][7] = 0.f; }
+}
+
+#ifdef SR_CORE_TIMING  // experiments (tools/ab_core.sh -DSR_CORE_TIMING): shader cycles of the core / the prologue per wave instead of sigma / sun_v
+__device__ __forceinline__ void core_timing_store(const FwdParams& prm, long tile, int lane, uint64_t t_kernel0, uint64_t t_core0, uint64_t r_core0) {
+  const uint64_t t_core1 = __builtin_amdgcn_s_memtime();
+  const uint64_t r_core1 = __builtin_amdgcn_s_memrealtime();
+  if (lane == 0 && prm.sigma && prm.sun_v) {
+    prm.sigma[tile] = (float)(t_core1 - t_core0);
+    prm.sun_v[tile] = (float)(t_core0 - t_kernel0);
+    if (prm.beta) prm.beta[tile] = (float)(r_core1 - r_core0);  // constant 100 MHz ticks
+  }
+}
+#endif
 
 // acc = the 5-row head accumulator (rows 0..2 albedo logits, 3 sun visibility logit on lanes < 32; row 0 = beta on lanes >= 32),
 // sig = sigma pre-activation.  REND: r_z .. = kRendFloats * NW * 32 floats of LDS (depth, sigma, sun, albedo, beta per point).

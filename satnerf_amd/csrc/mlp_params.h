@@ -5,6 +5,12 @@
 
 namespace sr {
 
+// waves per workgroup of the fused forward kernels, each wave one 32-point tile: the kernels take (or static_assert) their NW from
+// these, sr_render_points_per_block answers from them
+constexpr int kFwdWaves256 = 8;     // width 256, bf16 / fp16 operands: two waves per SIMD
+constexpr int kFwdWavesParity = 4;  // width 256, parity mode: one wave per SIMD with the 512-register file
+constexpr int kFwdWaves512 = 4;     // width 512: likewise
+
 // the fused render pass around the MLP (csrc/mlp_fwd.inc REND): stratified sampling in the prologue, the sky head and the
 // sigma->alpha compositing of the workgroup's rays in the epilogue.  rays == NULL: plain MLP launch.
 struct RenderParams {

@@ -214,11 +214,8 @@ __global__ void __launch_bounds__(256) wgrad9_kernel(const Wgrad9Params prm) {
     const int src = __builtin_amdgcn_readfirstlane(du[kDutyInts * k]), unit = __builtin_amdgcn_readfirstlane(du[kDutyInts * k + 1]);
     const int dst = __builtin_amdgcn_readfirstlane(du[kDutyInts * k + 2]), sc = __builtin_amdgcn_readfirstlane(du[kDutyInts * k + 3]);
     const char* ws = src == 1 ? prm.dpre : prm.acts;
-    auto uni64 = [](uint64_t v) {
-      return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    };
-    base[k] = uni64((uint64_t)(uintptr_t)(ws + (long)unit * 1024));
-    if (k < 4) sbase[k] = uni64((uint64_t)(uintptr_t)(ws + (long)(sc >> 4) * 1024 + (sc & 15)));
+    base[k] = uniform64(ws + (long)unit * 1024);
+    if (k < 4) sbase[k] = uniform64(ws + (long)(sc >> 4) * 1024 + (sc & 15));
     wb[k] = ring + (uint32_t)dst * kFrag9;
     on[k] = dst != kDumpFrag;
     if (k == 4) raw_src = src;

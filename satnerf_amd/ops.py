@@ -6,6 +6,7 @@ an entry is defined to take (e.g. ``lanczos_tables``).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -33,6 +34,18 @@ class KernelTimer:
 
 
 kernel_timer = None  # set to a KernelTimer to time the fused-MLP launches
+
+
+@contextlib.contextmanager
+def _timed(name):
+    """A ``kernel_timer`` span around the launches of the block (nothing when no timer is set)."""
+    if kernel_timer is None:
+        yield
+        return
+    e0, e1 = kernel_timer.span(name)
+    e0.record()
+    yield
+    e1.record()
 
 
 def _stream():
@@ -147,13 +160,9 @@ def satnerf_mlp(org, direction, sun, z, temb, ts, n_points, n_samples, feat, tau
     sun_v = torch.empty(n_points, dtype=torch.float32, device=dev)
     beta = torch.empty(n_points, dtype=torch.float32, device=dev)
     inp = _lib.MlpInputs(_p(org), so, _p(direction), sd, _p(sun), ss, _p(z), _p(temb), _p(ts), n_points, n_samples)
-    ev = kernel_timer.span("mlp_fwd") if kernel_timer is not None else None
-    if ev:
-        ev[0].record()
-    _lib.call("sr_satnerf_mlp_fwd", C.byref(inp), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), _p(albedo), _p(sigma),
-              _p(sun_v), _p(beta), _p(acts), int(fmt), _stream())
-    if ev:
-        ev[1].record()
+    with _timed("mlp_fwd"):
+        _lib.call("sr_satnerf_mlp_fwd", C.byref(inp), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), _p(albedo), _p(sigma),
+                  _p(sun_v), _p(beta), _p(acts), int(fmt), _stream())
     return albedo, sigma, sun_v, beta
 
 
@@ -189,12 +198,8 @@ def render_fwd(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_lo,
                            _p(_chk(sky_w1, "w1")), _p(_chk(sky_b1, "b1")), _p(_chk(sky_w2, "w2")), _p(_chk(sky_b2, "b2")), int(bank_chunks))
     outs = _lib.RenderOutputs(_p(out["z"]) if z is None else None, _p(out["albedo"]), None, _p(out["sun_v"]), _p(out["beta"]), _p(out["sky"]),
                               _p(out["weights"]), _p(out["transparency"]), _p(out["depth"]), _p(out["rgb"]))
-    ev = kernel_timer.span("mlp_fwd") if kernel_timer is not None else None
-    if ev:
-        ev[0].record()
-    _lib.call("sr_satnerf_render_fwd", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs), _stream())
-    if ev:
-        ev[1].record()
+    with _timed("mlp_fwd"):
+        _lib.call("sr_satnerf_render_fwd", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs), _stream())
     return out
 
 
@@ -236,13 +241,9 @@ def render_train(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_l
                         _p(out["d_sigma"]), _p(out["d_albedo"]), _p(out["d_sun"]), _p(out["g_beta"]), _p(out["d_sky"]),
                         _p(g.get("idx")), _p(_chk(g.get("cursor"), "cursor", allow_none=True)), int(g.get("batches", 0)),
                         *([_p(t) for t in g["out"]] if gather is not None else [None, None, None]))
-    ev = kernel_timer.span("mlp_fwd") if kernel_timer is not None else None
-    if ev:
-        ev[0].record()
-    _lib.call("sr_satnerf_render_train", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs),
-              C.byref(tr), _p(acts), 8, _stream())
-    if ev:
-        ev[1].record()
+    with _timed("mlp_fwd"):
+        _lib.call("sr_satnerf_render_train", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs),
+                  C.byref(tr), _p(acts), 8, _stream())
     return out
 
 
@@ -630,14 +631,10 @@ def satnerf_mlp_bwd(feat, tau, n_points, bwd_stream, acts, albedo, sigma, sun_v,
     dpre = _ws_empty(n_elems, torch.int16, dev, 2)
     d_t = torch.empty(n_points, tau, dtype=torch.float32, device=dev) if want_dt else None
     opt = lambda t, nm: _p(_chk(t, nm, allow_none=True))  # noqa: E731
-    ev = kernel_timer.span("mlp_bwd") if kernel_timer is not None else None
-    if ev:
-        ev[0].record()
-    _lib.call("sr_satnerf_mlp_bwd", feat, tau, n_points, _p(bwd_stream), _p(acts), _p(_chk(albedo, "albedo")), _p(_chk(sigma, "sigma")),
-              _p(_chk(sun_v, "sun_v")), _p(_chk(beta, "beta")), opt(g_albedo, "g_albedo"), opt(g_sigma, "g_sigma"), opt(g_sun_v, "g_sun_v"),
-              opt(g_beta, "g_beta"), _p(dpre), _p(d_t), int(fmt), _stream())
-    if ev:
-        ev[1].record()
+    with _timed("mlp_bwd"):
+        _lib.call("sr_satnerf_mlp_bwd", feat, tau, n_points, _p(bwd_stream), _p(acts), _p(_chk(albedo, "albedo")), _p(_chk(sigma, "sigma")),
+                  _p(_chk(sun_v, "sun_v")), _p(_chk(beta, "beta")), opt(g_albedo, "g_albedo"), opt(g_sigma, "g_sigma"), opt(g_sun_v, "g_sun_v"),
+                  opt(g_beta, "g_beta"), _p(dpre), _p(d_t), int(fmt), _stream())
     return dpre, d_t
 
 
@@ -671,16 +668,12 @@ def wgrad_partials(feat, tau, n_points, dpre, acts, blocks, fmt=16, loads=None, 
     plan, n_slices, span = wgrad_plan(blocks, n_points, n_wg=n_wg, fmt=fmt)
     block_floats = 256 * 256 + 256 * 32  # csrc/mlp_layout.h kWgBlockFloats
     partial = _ws_empty(n_slices * block_floats, torch.float32, dpre.device, 3)
-    ev = kernel_timer.span("wgrad") if kernel_timer is not None else None
-    if ev:
-        ev[0].record()
-    if int(fmt) == 8:
-        _lib.call("sr_satnerf_wgrad8", feat, tau, n_points, _p(dpre), dpre.numel(), _p(acts), _p(plan), _p(_chk(loads, "loads", torch.int32)), plan.shape[0], n_slices,
-                  span, _p(partial), _stream())
-    else:
-        _lib.call("sr_satnerf_wgrad", feat, tau, n_points, _p(dpre), _p(acts), _p(plan), plan.shape[0], n_slices, _p(partial), _stream())
-    if ev:
-        ev[1].record()
+    with _timed("wgrad"):
+        if int(fmt) == 8:
+            _lib.call("sr_satnerf_wgrad8", feat, tau, n_points, _p(dpre), dpre.numel(), _p(acts), _p(plan), _p(_chk(loads, "loads", torch.int32)), plan.shape[0],
+                      n_slices, span, _p(partial), _stream())
+        else:
+            _lib.call("sr_satnerf_wgrad", feat, tau, n_points, _p(dpre), _p(acts), _p(plan), plan.shape[0], n_slices, _p(partial), _stream())
     return partial, plan
 
 
