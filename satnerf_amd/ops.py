@@ -248,6 +248,8 @@ def render_train(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_l
 
 
 def composite(z, sigma, noise, noise_std, albedo, sun_v, sky_rgb, clamp_rgb=True):
+    """Compositing forward: (weights (N,S), transparency (N,S), depth (N,), rgb (N,3)).  ``albedo`` None = sigma-only (rgb is zero), as
+    composite_bwd takes it; ``sun_v`` / ``sky_rgb`` are given together or not at all (irradiance 1)."""
     n, s = z.shape
     dev = z.device
     _chk(z, "z"), _chk(sigma, "sigma")
@@ -255,7 +257,7 @@ def composite(z, sigma, noise, noise_std, albedo, sun_v, sky_rgb, clamp_rgb=True
     transp = torch.empty(n, s, dtype=torch.float32, device=dev)
     depth = torch.empty(n, dtype=torch.float32, device=dev)
     rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    _lib.call("sr_composite_fwd", _p(z), _p(sigma), _p(_chk(noise, "noise", allow_none=True)), float(noise_std), _p(_chk(albedo, "albedo")),
+    _lib.call("sr_composite_fwd", _p(z), _p(sigma), _p(_chk(noise, "noise", allow_none=True)), float(noise_std), _p(_chk(albedo, "albedo", allow_none=True)),
               _p(_chk(sun_v, "sun_v", allow_none=True)), _p(_chk(sky_rgb, "sky", allow_none=True)), n, s, int(clamp_rgb), _p(weights), _p(transp),
               _p(depth), _p(rgb), _stream())
     return weights, transp, depth, rgb

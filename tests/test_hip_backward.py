@@ -20,16 +20,18 @@ def test_composite_backward_matches_autograd():
     z = torch.sort(torch.rand(n, s, generator=g), -1)[0]
     sigma = (torch.randn(n, s, generator=g) * 3).requires_grad_(True)
     noise = torch.randn(n, s, generator=g)
-    albedo = torch.rand(n, s, 3, generator=g).requires_grad_(True)
+    albedo = torch.rand(n, s, 3, generator=g)
+    albedo[:24] *= 1.8  # the clamp bites on some of these rays: the same scaled albedo goes to autograd and to the kernel
+    albedo.requires_grad_(True)
     sun = torch.rand(n, s, generator=g).requires_grad_(True)
     sky = torch.rand(n, 3, generator=g).requires_grad_(True)
     gr, gd, gw, gt = torch.randn(n, 3, generator=g), torch.randn(n, generator=g), torch.randn(n, s, generator=g), torch.randn(n, s, generator=g)
     w, t = O.alpha_composite(z, sigma, noise * 0.3)
     depth = torch.sum(w * z, -1)
     irr = sun.unsqueeze(-1) + (1 - sun.unsqueeze(-1)) * sky.unsqueeze(1)
-    rgb = torch.clamp(torch.sum(w.unsqueeze(-1) * albedo * irr, -2) * 1.7 - 0.1, 0, 1)  # scaled so the clamp bites on some rays
-    # the kernel clamps the plain sum; emulate the same by differentiating the un-scaled clamp separately
-    rgb = torch.clamp(torch.sum(w.unsqueeze(-1) * albedo * irr, -2), 0, 1)
+    colour = torch.sum(w.unsqueeze(-1) * albedo * irr, -2)
+    assert int((colour > 1).any(-1).sum()) >= 3 and int((colour <= 1).all(-1).sum()) >= 3  # clamped rays and unclamped rays
+    rgb = torch.clamp(colour, 0, 1)
     ((rgb * gr).sum() + (depth * gd).sum() + (w * gw).sum() + (t * gt).sum()).backward()
     d = lambda x: x.detach().to(DEV).contiguous()  # noqa: E731
     wg, tg, _, _ = ops.composite(d(z), d(sigma), d(noise), 0.3, d(albedo), d(sun), d(sky))
