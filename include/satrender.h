@@ -172,6 +172,22 @@ int sr_satnerf_render_fwd(const sr_render_args* in, int feat, int tau, int mode,
 /* points a workgroup of the fused kernel owns (256 / 128), or -1 when (feat, mode) has no fused build */
 int sr_render_points_per_block(int feat, int mode);
 
+/* ---- depth-only ("geometry") render pass in ONE launch: rendering.py:62-81 -> the model's sigma_only cut, models/satnerf.py:183-185
+ *      (fc_net and sigma_from_xyz, no feats, no colour / sun / uncertainty head) -> the sigma -> alpha -> weights -> depth half of
+ *      models/satnerf.py:52-67; no sky head (:138-143), no rgb.  With SR_MODE_BF16 / SR_MODE_F16 the launch runs the trunk-and-sigma core,
+ *      which reads the SAME packed stream as sr_satnerf_render_fwd (it jumps over the feats pieces) and none of the sky weights (sky_* may
+ *      be NULL); depth, weights, transparency, z_vals and sigma are those of sr_satnerf_render_fwd on the same inputs, bit for bit.
+ *      SR_MODE_BF16X3, and every mode under SATNERF_FWD_V1=1, run the full kernel with the unused outputs NULL (then sky_* are required).
+ * Reads and writes only these fields of `out`: z_vals (N,S) [NULL ok], sigma (N,S) [NULL ok], weights (N,S), transparency (N,S), depth (N).
+ * Preconditions as sr_satnerf_render_fwd: n_samples >= 2 and n_samples divides sr_render_points_per_block(feat, mode); tick is 0 or 1. */
+int sr_satnerf_render_depth(const sr_render_args* in, int feat, int tau, int mode, const uint16_t* stream_hi, const uint16_t* stream_lo,
+                            const float* l0, const sr_render_outputs* out, void* stream);
+
+/* ---- sigma of the fused MLP over points: SatNeRF.forward(..., sigma_only=True), models/satnerf.py:183-185, as the point launch
+ *      sr_satnerf_mlp_fwd (same inputs, stream and l0) restricted to the trunk and the sigma row: sigma (P), bit-equal to that launch's. */
+int sr_satnerf_mlp_sigma(const sr_mlp_inputs* in, int feat, int tau, int mode, const uint16_t* stream_hi, const uint16_t* stream_lo,
+                         const float* l0, float* sigma, void* stream);
+
 /* ---- the training forward in ONE launch: replaces main.py:60-75,127 + metrics.py:21-25,36-44,56-73 + autograd through the compositing ---
  * sr_satnerf_render_train = sr_ray_setup + sr_satnerf_mlp_fwd (saving the SR_FMT8 activations) + sr_render_loss: the render pass above
  * with, in its epilogue, the colour loss (SatNerfLoss; SNerfLoss while sched[2] != 0) and the closed-form compositing backward of every

@@ -60,6 +60,8 @@ SIGNATURES = {
     "sr_act_elems_per_tile": (_i64, [_i, _i]),
     "sr_satnerf_render_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sr_render_points_per_block": (_i, [_i, _i]),
+    "sr_satnerf_render_depth": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sr_satnerf_mlp_sigma": (_i, [C.POINTER(MlpInputs), _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sr_satnerf_render_train": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sr_pack_stream": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sr_dpre_elems_per_tile": (_i64, [_i, _i]),

@@ -15,7 +15,11 @@ this file states what is particular to the width-256 core (one wave = 32 points,
   * the epilogue of tile t-1 is 16 v_sin in place on its accumulator and 8 v_cvt_pk into the next stage's B fragments (VGPRs);
   * fc_net.0 (K = 3, fp32 inputs) rides the matrix pipe too: the kernel prologue splits x, y, z and the fc_net.0 rows three ways into
     bf16 (h + m + l = 24 bits) and lays the 21 significant cross products over two k-steps (``l0_terms``), so pieces 0..15 of the ring
-    are written by the prologue (not by LDS-DMA) and the stream starts with 8 two-MFMA tiles (always the bf16 opcode, MF0).
+    are written by the prologue (not by LDS-DMA) and the stream starts with 8 two-MFMA tiles (always the bf16 opcode, MF0);
+  * ``Core(auxs, heads=False)`` is the geometry variant (depth-only rendering): L0..L7 and the sigma tile of the SAME packed stream -- the
+    DMA source offset jumps over the feats rows (stream_common.py SRC_JUMP) -- written to csrc/mlp_fwd_core_a{1,2}g.inc by the build, their
+    text pinned by the committed digests of gen/variant_streams.sha256 (stream_common.py variant_files), checked by
+    tests/test_fwd_core_geometry.py.
 """
 from __future__ import annotations
 
@@ -25,7 +29,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stream_common import CoreBase, LaneModel, Tile, aux_steps, bf16_bits, bf16_to_f32, f32_to_frag, main  # noqa: E402,F401
+from stream_common import (CoreBase, LaneModel, Tile, aux_steps, bf16_bits, bf16_to_f32, f32_to_frag, feats_jump, file_digest, main, read_digests,  # noqa: E402,F401
+                           variant_files, write_variants)
 
 # ---- register map (VGPR numbers) ------------------------------------------------------------------------------------------------
 X, Y = 0, 64            # the two 64-register activation vectors (16 B fragments of 4 registers)
@@ -49,8 +54,9 @@ KS, HS = 16, 8          # k-steps of a 256-wide / 128-wide input
 NW = 8                  # waves per workgroup = pieces per DMA row
 
 
-def stage_list(auxs):
-    """The chunk list of FwdStream<AUXS> (mlp_layout.h) with the register assignment of this kernel."""
+def stage_list(auxs, heads=True):
+    """The chunk list of FwdStream<AUXS> (mlp_layout.h) with the register assignment of this kernel.  heads=False: the geometry
+    variant, L0..L7 and the sigma tile (its units are numbered on from L7's: the feats pieces between them are jumped over)."""
     tiles, p, tno = [], 0, 0
     auxb = [AUX + 4 * a for a in range(auxs)]
 
@@ -79,8 +85,11 @@ def stage_list(auxs):
     assert p == L0_PIECES
     for l in range(7):
         dense(X if l % 2 == 0 else Y, KS, 8, "sin", Y if l % 2 == 0 else X, f"L{l + 1}", 8 * (l + 1))
-    dense(Y, KS, 8, "id", X, "feats", 64)      # a7 (in Y) -> feats (in X)
+    if heads:
+        dense(Y, KS, 8, "id", X, "feats", 64)  # a7 (in Y) -> feats (in X)
     dense(Y, KS, 1, "sigma", None, "sigma")
+    if not heads:
+        return tiles, p
     dense(X, KS, 4, "sin", H0, "rgbh", 72)
     head(H0, False, "Hr")
     dense(X, KS, 4, "sin", H1, "s1", 76)
@@ -97,16 +106,31 @@ class Core(CoreBase):
     MT, MTH, SAVE, AR0, NA, SCALE_DWORDS = 8, 4, 8, AR0, NA, 2
     VL, VOFF, HEAD, SIG, SV, SOFF, KMAGIC, EB, MXT, K128 = (VL0, VL1), VOFF, HEAD, SIG, SV, SOFF, KMAGIC, EB, MXT, K128
     stage_list = staticmethod(stage_list)
+    VARIANTS = ((dict(heads=False), "g"),)
 
-    def __init__(self, auxs, R=128, PF=5, GROUP=2, FILL=None, ablate=(), save=0):
+    def __init__(self, auxs, R=128, PF=5, GROUP=2, FILL=None, ablate=(), save=0, heads=True):
+        self.heads = heads
+        if not heads:  # sigma's rows are fed from behind the feats rows of the one packed forward stream
+            assert save == 0, "the geometry core saves nothing"
+            self.stage_list = lambda a: stage_list(a, heads=False)
+            self.SRC_JUMP = feats_jump(stage_list(auxs)[0], NW)
         super().__init__(auxs, R, PF, GROUP, FILL, ablate, save)
 
     def text(self):
         if "empty" in self.ablate:
-            return ["s_mov_b32 %[m0save], m0", f"v_mov_b32 v{SIG}, 0"] + [f"v_mov_b32 v{HEAD + g}, 0" for g in range(16)]
+            return ["s_mov_b32 %[m0save], m0", f"v_mov_b32 v{SIG}, 0"] + [f"v_mov_b32 v{HEAD + g}, 0" for g in range(16 if self.heads else 0)]
         return super().text()
 
     def header(self):
+        if not self.heads:
+            row, rows = self.SRC_JUMP
+            return ["// GENERATED by csrc/gen/fwd_core.py by the build -- do not edit (its text is pinned by csrc/gen/variant_streams.sha256; tests/test_fwd_core_geometry.py).",
+                    f"// geometry (trunk + sigma) forward core, AUXS = {self.auxs}: {self.stats['mfma']} MFMAs, {self.stats['instructions']} instructions, "
+                    f"{self.stats['barriers']} rendezvous, {self.stats['rows']} LDS-DMA rows, ring of {self.R} pieces, A fragments {self.PF} ahead.",
+                    f"// Reads the packed forward stream of the full core unchanged: behind ring row {row - 1} (L7's last) the source offset jumps over the",
+                    f"// {rows} rows of feats pieces, so ring rows {row}.. are the sigma tile's.  No head accumulator: the one output is v{SIG}.",
+                    f"// Ring pieces 0..{L0_PIECES - 1} (fc_net.0) are written by the kernel prologue; stream piece p is ring piece p + {L0_PIECES}.",
+                    "// Operands: %[sb] stream base (SGPR pair), %[wb] LDS ring address + wave * 1024, %[wave] wave index, %[m0save] scratch SGPR"]
         return ["// GENERATED by csrc/gen/fwd_core.py -- do not edit (tests/test_fwd_core.py checks it is current).",
                 f"// fused forward core, AUXS = {self.auxs}: {self.stats['mfma']} MFMAs, {self.stats['instructions']} instructions, "
                 f"{self.stats['barriers']} rendezvous, {self.stats['rows']} LDS-DMA rows, ring of {self.R} pieces, A fragments {self.PF} ahead.",
@@ -188,5 +212,7 @@ class Machine(LaneModel):
     """the width-256 core on the shared lane model: ring pieces 0..15 (fc_net.0) are in the ring when the stream starts"""
 
 
+STEM = "mlp_fwd_core"  # csrc/<STEM>_a<auxs>[s<save> | g].inc
+
 if __name__ == "__main__":
-    sys.exit(main(Core, "mlp_fwd_core", __doc__, R=128, PF=5, GROUP=2, FILL=None))
+    sys.exit(main(Core, STEM, __doc__, R=128, PF=5, GROUP=2, FILL=None))

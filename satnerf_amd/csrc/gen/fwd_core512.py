@@ -22,7 +22,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stream_common import A0, CoreBase, LaneModel, Tile, aux_steps, bf16_bits, f32_to_frag, main, rn  # noqa: E402,F401
+from stream_common import A0, CoreBase, LaneModel, Tile, aux_steps, bf16_bits, f32_to_frag, feats_jump, file_digest, main, read_digests, rn, variant_files, write_variants  # noqa: E402,F401
 
 FEAT = 512
 KS, HS, MT, MTH, NW = FEAT // 16, FEAT // 32, FEAT // 32, FEAT // 64, 4
@@ -44,8 +44,9 @@ N_AGPR = 176
 IN_AUX, OUT_HEAD = 144, 128   # operands arrive / leave in VGPRs: aux fragments in v[144:151], head accumulator out in v[128:143]
 
 
-def stage_list(auxs):
-    """the chunk list of FwdStream<AUXS> at SR_FEAT = 512 (mlp_layout.h) with this kernel's register assignment"""
+def stage_list(auxs, heads=True):
+    """the chunk list of FwdStream<AUXS> at SR_FEAT = 512 (mlp_layout.h) with this kernel's register assignment.  heads=False: the
+    geometry variant, L1..L7 and the sigma tile (its units are numbered on from L7's: the feats pieces between them are jumped over)."""
     tiles, p, tno = [], 0, 0
     auxb = [AUX + 4 * a for a in range(auxs)]
 
@@ -70,8 +71,11 @@ def stage_list(auxs):
     H0, H1 = Y, Y + 4 * HS
     for l in range(7):
         dense(X if l % 2 == 0 else Y, KS, MT, "sin", Y if l % 2 == 0 else X, f"L{l + 1}", MT * (l + 1))
-    dense(Y, KS, MT, "id", X, "feats", 8 * MT)
+    if heads:
+        dense(Y, KS, MT, "id", X, "feats", 8 * MT)
     dense(Y, KS, 1, "sigma", None, "sigma")
+    if not heads:
+        return tiles, p
     dense(X, KS, MTH, "sin", H0, "rgbh", 9 * MT)
     head(H0, False, "Hr")
     dense(X, KS, MTH, "sin", H1, "s1", 9 * MT + MTH)
@@ -88,8 +92,15 @@ class Core512(CoreBase):
     MT, MTH, SAVE, AR0, NA, OUT_HEAD, SCALE_DWORDS = MT, MTH, 8, AR0, NA, OUT_HEAD, 4
     VL, VOFF, HEAD, SIG, TMP, SV, SOFF, KMAGIC, EB, MXT, K128 = VL, VOFF, HEAD, SIG, TMP, SV, SOFF, KMAGIC, EB, MXT, K128
     stage_list = staticmethod(stage_list)
+    VARIANTS = ((dict(heads=False), "g"),)
 
-    def __init__(self, auxs, R=144, PF=5, GROUP=1, FILL=None, ablate=(), save=0):
+    def __init__(self, auxs, R=144, PF=5, GROUP=1, FILL=None, ablate=(), save=0, heads=True):
+        self.heads = heads
+        if not heads:  # sigma's rows are fed from behind the feats rows of the one packed forward stream; no head accumulator to copy out
+            assert save == 0, "the geometry core saves nothing"
+            self.stage_list = lambda a: stage_list(a, heads=False)
+            self.SRC_JUMP = feats_jump(stage_list(auxs)[0], NW)
+            self.OUT_HEAD = None
         super().__init__(auxs, R, PF, GROUP, FILL, ablate, save)
 
     def preamble(self):
@@ -98,6 +109,14 @@ class Core512(CoreBase):
 
     def header(self):
         s = self.stats
+        if not self.heads:
+            row, rows = self.SRC_JUMP
+            return ["// GENERATED by csrc/gen/fwd_core512.py by the build -- do not edit (its text is pinned by csrc/gen/variant_streams.sha256; tests/test_fwd_core_geometry.py).",
+                    f"// width-512 geometry (trunk + sigma) forward core, AUXS = {self.auxs}: {s['mfma']} MFMAs, {s['instructions']} instructions, "
+                    f"{s['barriers']} rendezvous, {s['rows']} LDS-DMA rows, ring of {self.R} pieces, A fragments {self.PF} ahead.",
+                    f"// Reads the packed forward stream of the full core unchanged: behind ring row {row - 1} (L7's last) the source offset jumps over the",
+                    f"// {rows} rows of feats pieces, so ring rows {row}.. are the sigma tile's.  No head accumulator: the one output is v{SIG}.",
+                    "// Operands: %[sb] stream base (SGPR pair), %[wb] LDS ring address + wave * 1024, %[wave] wave index, %[m0save] scratch SGPR"]
         return ["// GENERATED by csrc/gen/fwd_core512.py -- do not edit (tests/test_fwd_core.py checks it is current).",
                 f"// width-512 forward core, AUXS = {self.auxs}: {s['mfma']} MFMAs, {s['instructions']} instructions, {s['barriers']} rendezvous, "
                 f"{s['rows']} LDS-DMA rows, ring of {self.R} pieces, A fragments {self.PF} ahead.",
@@ -118,5 +137,7 @@ class Machine512(LaneModel):
     """the width-512 core on the shared lane model"""
 
 
+STEM = "mlp_fwd512_core"  # csrc/<STEM>_a<auxs>[s<save> | g].inc
+
 if __name__ == "__main__":
-    sys.exit(main(Core512, "mlp_fwd512_core", __doc__, PF=5, GROUP=1, FILL=None))
+    sys.exit(main(Core512, STEM, __doc__, PF=5, GROUP=1, FILL=None))

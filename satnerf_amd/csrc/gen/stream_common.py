@@ -57,6 +57,15 @@ class Tile:
         self.acc, self.c0, self.epi, self.out, self.name = acc, c0, epi, out, name
 
 
+def feats_jump(tiles, nw):
+    """SRC_JUMP of a variant that leaves the feats tiles out of the full stage list `tiles`: (first ring row of what follows them, rows
+    of feats pieces).  Every trunk layer is whole DMA rows, so the jump is row-aligned."""
+    p0 = next(t.p0 for t in tiles if t.name == "feats.0")
+    p1 = next(t.p0 for t in tiles if t.name == "sigma.0")
+    assert p0 % nw == 0 and p1 % nw == 0, "the feats pieces are not whole DMA rows"
+    return p0 // nw, (p1 - p0) // nw
+
+
 # =================================================================================================================================
 # The scheduler
 # =================================================================================================================================
@@ -74,6 +83,9 @@ class CoreBase:
     TMP = ()
     WS = "ab"             # the workspace operand of the stores
     KEEP_FIRST = ("m0", "dma", "voff")   # what `nodma` leaves in front of the first rendezvous (the first reads need those requests)
+    SRC_JUMP = None       # (row, rows): ring rows >= row are fed from stream rows `rows` further on (a variant that leaves stages out)
+    VARIANTS = ()         # (constructor keywords, file suffix) of the further SAVE = 0 streams main() writes
+    heads = True          # False (an instance attribute of the cores that offer it): the stream ends with the sigma tile, see tail()
 
     def __init__(self, auxs, R, PF, GROUP, FILL, ablate, save):
         assert R % self.NW == 0 and R * 1024 * len(self.SRC) <= 65536 * len(self.VL) and PF + 1 <= self.NA and save in (0, self.SAVE)
@@ -94,6 +106,10 @@ class CoreBase:
         c = "0" if c0 else rn(acc, 16)
         self._e("mfma", (acc, areg, breg, c0), f"{op} {rn(acc, 16)}, {rn(areg, 4)}, {rn(breg, 4)}, {c}")
 
+    def src_row(self, j):
+        """the row of the packed stream that ring row j is fed from"""
+        return j if self.SRC_JUMP is None or j < self.SRC_JUMP[0] else j + self.SRC_JUMP[1]
+
     def dsread(self, dst, slot, plane):
         unit = 1024 * len(self.SRC)          # a ring slot holds every plane of its unit; one read base register per 64 KiB of ring
         per_base = 65536 // unit
@@ -104,7 +120,7 @@ class CoreBase:
 
     def dma_request(self, j, plane, partial):
         """request `plane` of row j: wave w fetches that plane of unit NW j + w into ring slot (NW j + w) % R from the stream offset VOFF
-        holds (w * 1024 + lane * 16 + (j - PRE_ROWS) * NW * 1024; advanced behind the row's last request).  A ragged last row (waves >=
+        holds (w * 1024 + lane * 16 + (src_row(j) - PRE_ROWS) * NW * 1024; advanced behind the row's last request).  A ragged last row (waves >=
         partial skip it: s_cbranch around the requests, SCC from s_cmp) is emitted whole under one branch."""
         planes = len(self.SRC)
         imm = ((self.NW * j) % self.R) * 1024 * planes + 1024 * plane
@@ -119,7 +135,8 @@ class CoreBase:
         if plane == planes - 1:
             if partial is not None:
                 self._e("label", (j,), f"{label}:")
-            self._e("voff", (), f"v_add_u32 v{self.VOFF}, 0x{self.VOFF_STEP:x}, v{self.VOFF}")
+            rows = self.src_row(j + 1) - self.src_row(j)  # 1, or past the stages a variant leaves out
+            self._e("voff", () if rows == 1 else (rows,), f"v_add_u32 v{self.VOFF}, 0x{rows * self.VOFF_STEP:x}, v{self.VOFF}")
 
     # ---- the loads in flight, oldest first: ("row", j) per DMA request, a core's own tags for its register loads --------------------------
     def vm_wait(self, tag):
@@ -354,6 +371,12 @@ class CoreBase:
 
     def tail(self):
         """behind the last MFMA: the head accumulator is read right behind it (by compiler code or here)"""
+        if not self.heads:  # the last tile is sigma's: its move to SIG waits out XDL write -> VALU read (LaneModel.XDL_NOPS)
+            self._e("nop", (15,), "s_nop 15")
+            self._e("nop", (3,), "s_nop 3")
+            while self.epi_q:
+                self._pop_epi()
+            return
         assert not self.epi_q
         self._e("nop", (15,), "s_nop 15")
         if self.OUT_HEAD is not None:
@@ -470,8 +493,50 @@ class CoreBase:
         return "\n".join(lines) + "\n"
 
 
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "variant_streams.sha256")
+
+
+def variant_files(cls, stem):
+    """the file names of the class's VARIANTS (SAVE = 0, both aux sizes).  Their text is not in git; the committed DIGESTS file pins it:
+    one ``<sha256>  <file name>`` line per file, which the build holds what it writes to and tests/test_fwd_core_geometry.py holds the
+    generator to, so a change of a stream shows in history as a change of its line."""
+    return [f"{stem}_a{auxs}{suffix}.inc" for _, suffix in cls.VARIANTS for auxs in (1, 2)]
+
+
+def read_digests():
+    with open(DIGESTS) as f:
+        return {name: digest for digest, name in (line.split() for line in f if line.strip())}
+
+
+def file_digest(path):
+    import hashlib
+
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
+
+
+def write_variants(cls, stem, out_dir, record=False, **kw):
+    """write the VARIANTS' streams into out_dir, each file in one step (another build may be reading it); ``record``: enter their
+    digests into DIGESTS (the generators' command line with the default schedule does).  Returns [(path, core)]."""
+    out = []
+    for vkw, suffix in cls.VARIANTS:
+        for auxs in (1, 2):
+            c = cls(auxs, save=0, **kw, **vkw)
+            path = os.path.join(out_dir, f"{stem}_a{auxs}{suffix}.inc")
+            with open(f"{path}.tmp{os.getpid()}", "w") as f:
+                f.write(c.inc_file())
+            os.replace(f.name, path)
+            out.append((path, c))
+    if record:
+        pins = read_digests() if os.path.exists(DIGESTS) else {}
+        pins.update({os.path.basename(path): file_digest(path) for path, _ in out})
+        with open(DIGESTS, "w") as f:
+            f.writelines(f"{pins[name]}  {name}\n" for name in sorted(pins))
+    return out
+
+
 def main(cls, stem, doc, **defaults):
-    """the generators' command line: writes <stem>_a{1,2}[s<save>].inc and the two clobber lists; `defaults` names the schedule
+    """the generators' command line: writes <stem>_a{1,2}[s<save>].inc, the class's VARIANTS and the two clobber lists; `defaults` names the schedule
     parameters the core's constructor takes (R, PF, GROUP, FILL)"""
     import argparse
 
@@ -490,6 +555,10 @@ def main(cls, stem, doc, **defaults):
             with open(path, "w") as f:
                 f.write(c.inc_file())
             print(path, c.stats)
+    stock = not a.ablate and all(getattr(a, name) == value for name, value in defaults.items())  # the streams the kernels are built from
+    for path, c in write_variants(cls, stem, out_dir, record=stock, ablate=[x for x in a.ablate.split(",") if x],
+                                  **{name: getattr(a, name) for name in defaults}):
+        print(path, c.stats)
     for save in sorted({0, cls.SAVE}):
         with open(os.path.join(out_dir, f"{stem}_clobbers{f'_s{save}' if save else ''}.inc"), "w") as f:
             f.write(cls.clobber_file(save))
@@ -666,7 +735,7 @@ class LaneModel:
             elif op == "dma":
                 j, plane, partial = a
                 assert n - self._m0_at >= 2, "M0 write -> LDS-DMA needs one wait state"
-                assert c.PRE_ROWS + self.voff_rows == j, ("VOFF does not address row j of the stream", j, self.voff_rows)
+                assert c.PRE_ROWS + self.voff_rows == c.src_row(j), ("VOFF does not address row j of the stream", j, self.voff_rows)
                 self._vm_issue(("row", j, plane), ragged=partial is not None)
                 for w in range(NW if partial is None else partial):
                     u = NW * j + w
@@ -674,9 +743,9 @@ class LaneModel:
                     old = self.ring_unit[slot][plane]
                     assert old < 0 or self.consumed_before_barrier[old], ("DMA overwrites a unit not yet consumed by every wave", old, u)
                     self.ring_unit[slot][plane] = u
-                    self.ring[slot, plane] = self.stream[plane][u]
+                    self.ring[slot, plane] = self.stream[plane][NW * c.src_row(j) + w]
             elif op == "voff":
-                self.voff_rows += 1
+                self.voff_rows += a[0] if a else 1
             elif op == "fract":
                 self._valu_reads(a[0])
                 x = self.f(a[0]).astype(np.float64)

@@ -29,6 +29,8 @@ constexpr int kRing2 = 128;  // ring pieces (gen/fwd_core.py R)
 #define SR_CORE_A1S8 "mlp_fwd_core_a1s8.inc"
 #define SR_CORE_A2S8 "mlp_fwd_core_a2s8.inc"
 #endif
+#define SR_CORE_A1G "mlp_fwd_core_a1g.inc"  // the geometry cores (gen/fwd_core.py heads=False): trunk + sigma
+#define SR_CORE_A2G "mlp_fwd_core_a2g.inc"
 #define SR_CORE_MF0 ".macro MF0 d, a, b, c\n v_mfma_f32_32x32x16_bf16 \\d, \\a, \\b, \\c\n.endm\n"  // fc_net.0's split operands: bf16 in every mode
 #ifdef SR_F16
 #define SR_CORE_MACROS ".macro MF d, a, b, c\n v_mfma_f32_32x32x16_f16 \\d, \\a, \\b, \\c\n.endm\n.macro PK d, a, b\n v_cvt_pk_f16_f32 \\d, \\a, \\b\n.endm\n" SR_CORE_MF0
@@ -47,11 +49,14 @@ __device__ __forceinline__ void split3(float v, float& h, float& m, float& l) {
 
 // SAVE: 0 = inference, SR_FMT8 = the training forward (activations saved in the 8-bit workspaces of mlp_layout.h: the PHASE8 / MX8
 // encoding and the non-temporal stores are part of the generated stream)
-template <int AUXS, bool REND, int SAVE = 0>
+// GEOM: the geometry core -- fc_net.0 .. fc_net.14 and the sigma tile of the SAME packed stream (the feats rows are jumped over), no head
+// accumulator; with REND the depth-only render pass (models/satnerf.py:183-185 sigma_only + :52-67), mlp_fwd_io.inc write_outputs
+template <int AUXS, bool REND, int SAVE = 0, bool GEOM = false>
 __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) {
   constexpr int NW = kFwdWaves256;  // (gen/fwd_core.py feeds the ring in rows of 8)
   constexpr int AK = act8_units(AUXS);  // workspace units per tile (SAVE)
   static_assert(SAVE == 0 || SAVE == SR_FMT8, "the generated core saves in the 8-bit format only");
+  static_assert(!GEOM || SAVE == 0, "the geometry core saves nothing");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
   float* r_z = reinterpret_cast<float*>(smem + kRing2 * 1024);
@@ -137,7 +142,26 @@ __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) 
   const uint64_t ab = uniform64(prm.acts);
 #define SR_CORE_OUTS "={v[192:207]}"(acc), "={v208}"(sig), "+{v211}"(voff), [m0save] "=&s"(m0save)
 #define SR_CORE_INS "{v[232:235]}"(l0b0), "{v[236:239]}"(l0b1), "{v209}"(vl0), "{v210}"(vl1), [sb] "s"(sb), [wb] "s"(wb), [wave] "s"(wave)
-  if constexpr (AUXS == 1 && SAVE == 0) {
+  if constexpr (GEOM && AUXS == 1) {
+    asm volatile(SR_CORE_MACROS
+#include SR_CORE_A1G
+                 ".purgem MF\n.purgem PK\n.purgem MF0\n"
+                 : "={v208}"(sig), "+{v211}"(voff), [m0save] "=&s"(m0save)
+                 : "{v[184:187]}"(a0), SR_CORE_INS
+                 :
+#include "mlp_fwd_core_clobbers.inc"
+    );
+  } else if constexpr (GEOM) {
+    const u32x4 a1 = __builtin_bit_cast(u32x4, auxf[AUXS - 1]);
+    asm volatile(SR_CORE_MACROS
+#include SR_CORE_A2G
+                 ".purgem MF\n.purgem PK\n.purgem MF0\n"
+                 : "={v208}"(sig), "+{v211}"(voff), [m0save] "=&s"(m0save)
+                 : "{v[184:187]}"(a0), "{v[188:191]}"(a1), SR_CORE_INS
+                 :
+#include "mlp_fwd_core_clobbers.inc"
+    );
+  } else if constexpr (AUXS == 1 && SAVE == 0) {
     asm volatile(SR_CORE_MACROS
 #include SR_CORE_A1
                  ".purgem MF\n.purgem PK\n.purgem MF0\n"
@@ -183,12 +207,13 @@ __global__ void __launch_bounds__(512) satnerf_fwd2_kernel(const FwdParams prm) 
   core_timing_store(prm, tile, lane, t_kernel0, t_core0, r_core0);
   return;
 #endif
-  write_outputs<REND, NW>(prm, in, acc, sig, r_z, wave, lane);
+  write_outputs<REND, NW, GEOM>(prm, in, acc, sig, r_z, wave, lane);
 }
 
-template <int AUXS, bool REND, int SAVE = 0>
+template <int AUXS, bool REND, int SAVE = 0, bool GEOM = false>
 int launch_fwd2(const FwdParams& p, hipStream_t st) {
-  return launch_fwd_kernel(satnerf_fwd2_kernel<AUXS, REND, SAVE>, "satnerf_fwd2_kernel", kFwdWaves256, (size_t)kRing2 * 1024, REND ? kRendFloats : 0, p, st);
+  return launch_fwd_kernel(satnerf_fwd2_kernel<AUXS, REND, SAVE, GEOM>, GEOM ? "satnerf_fwd2_kernel (geometry)" : "satnerf_fwd2_kernel", kFwdWaves256,
+                           (size_t)kRing2 * 1024, !REND ? 0 : GEOM ? kRendFloatsGeom : kRendFloats, p, st);
 }
 
 // entry of the (1, AUXS) translation units: the generated core for inference and for the 8-bit training forward, unless
@@ -199,6 +224,15 @@ int launch_fwd_any(const FwdParams& p, int save_fmt, hipStream_t st) {
   if (route != FwdRoute::Core) return route == FwdRoute::Refused ? 1 : launch_fwd<1, AUXS>(p, save_fmt, st);
   if (save_fmt == SR_FMT8) return p.rend.rays != nullptr ? launch_fwd2<AUXS, true, SR_FMT8>(p, st) : launch_fwd2<AUXS, false, SR_FMT8>(p, st);
   return p.rend.rays != nullptr ? launch_fwd2<AUXS, true>(p, st) : launch_fwd2<AUXS, false>(p, st);
+}
+
+// entry of the geometry translation units (mlp_fwdg_*.hip): a launch that wants sigma alone (p.albedo / sun_v / beta and rend.rgb / sky
+// null).  fwd_route decides as for every inference launch; off the Core route `full` -- the (1, AUXS) unit's entry -- runs the request
+// with the unused outputs null: correct, and no faster.
+template <int AUXS>
+int launch_fwd_geom(const FwdParams& p, hipStream_t st, int (*full)(const FwdParams&, int, hipStream_t)) {
+  if (fwd_route(p, 0, SR_FMT8, act8_units(AUXS), true) != FwdRoute::Core) return full(p, 0, st);
+  return p.rend.rays != nullptr ? launch_fwd2<AUXS, true, 0, true>(p, st) : launch_fwd2<AUXS, false, 0, true>(p, st);
 }
 
 #endif  // SR_FEAT == 256

@@ -24,6 +24,8 @@ constexpr int kRing5 = 144;  // ring pieces of 1 KiB (gen/fwd_core512.py R)
 #define SR_CORE5_A1S8 "mlp_fwd512_core_a1s8.inc"
 #define SR_CORE5_A2S8 "mlp_fwd512_core_a2s8.inc"
 #endif
+#define SR_CORE5_A1G "mlp_fwd512_core_a1g.inc"  // the geometry cores (gen/fwd_core512.py heads=False): trunk + sigma
+#define SR_CORE5_A2G "mlp_fwd512_core_a2g.inc"
 #ifdef SR_F16
 #define SR_CORE5_MACROS ".macro MF d, a, b, c\n v_mfma_f32_32x32x16_f16 \\d, \\a, \\b, \\c\n.endm\n.macro PK d, a, b\n v_cvt_pk_f16_f32 \\d, \\a, \\b\n.endm\n"
 #else
@@ -37,11 +39,14 @@ __device__ __forceinline__ u32x32_5 cat8_5(const uint4* f) {
   return v;
 }
 
-template <int AUXS, bool REND, int SAVE = 0>
+// GEOM: the geometry core (as in mlp_fwd2.inc): trunk and sigma tile of the same packed stream, `acc` is then only the register operand
+// the stream uses as an accumulator
+template <int AUXS, bool REND, int SAVE = 0, bool GEOM = false>
 __global__ void __launch_bounds__(256) satnerf_fwd512g_kernel(const FwdParams prm) {
   constexpr int NW = kFwdWaves512;  // (gen/fwd_core512.py feeds the ring in rows of 4)
   constexpr int AK = act8_units(AUXS);  // workspace units per tile (SAVE)
   static_assert(SAVE == 0 || SAVE == SR_FMT8, "the generated core saves in the 8-bit format only");
+  static_assert(!GEOM || SAVE == 0, "the geometry core saves nothing");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
   float4* l0w = reinterpret_cast<float4*>(smem + kRing5 * 1024);
@@ -117,7 +122,25 @@ __global__ void __launch_bounds__(256) satnerf_fwd512g_kernel(const FwdParams pr
   "+{v[0:31]}"(x0), "+{v[32:63]}"(x1), "+{v[64:95]}"(x2), "+{v[96:127]}"(x3), "+{v[144:151]}"(auxv), "={v[128:143]}"(acc),            \
       "={v168}"(sig), "+{v172}"(voff), [m0save] "=&s"(m0save)
 #define SR_CORE5_INS "{v169}"(vl0), "{v170}"(vl1), "{v171}"(vl2), [sb] "s"(sb), [wb] "s"(wb), [wave] "s"(wave)
-  if constexpr (AUXS == 1 && SAVE == 0) {
+  if constexpr (GEOM && AUXS == 1) {
+    asm volatile(SR_CORE5_MACROS
+#include SR_CORE5_A1G
+                 ".purgem MF\n.purgem PK\n"
+                 : SR_CORE5_OUTS
+                 : SR_CORE5_INS
+                 :
+#include "mlp_fwd512_core_clobbers.inc"
+    );
+  } else if constexpr (GEOM) {
+    asm volatile(SR_CORE5_MACROS
+#include SR_CORE5_A2G
+                 ".purgem MF\n.purgem PK\n"
+                 : SR_CORE5_OUTS
+                 : SR_CORE5_INS
+                 :
+#include "mlp_fwd512_core_clobbers.inc"
+    );
+  } else if constexpr (AUXS == 1 && SAVE == 0) {
     asm volatile(SR_CORE5_MACROS
 #include SR_CORE5_A1
                  ".purgem MF\n.purgem PK\n"
@@ -161,13 +184,13 @@ __global__ void __launch_bounds__(256) satnerf_fwd512g_kernel(const FwdParams pr
   core_timing_store(prm, tile, lane, t_kernel0, t_core0, r_core0);
   return;
 #endif
-  write_outputs<REND, NW>(prm, in, acc, sig, r_z, wave, lane);
+  write_outputs<REND, NW, GEOM>(prm, in, acc, sig, r_z, wave, lane);
 }
 
-template <int AUXS, bool REND, int SAVE = 0>
+template <int AUXS, bool REND, int SAVE = 0, bool GEOM = false>
 int launch_fwd512g(const FwdParams& p, hipStream_t st) {
-  return launch_fwd_kernel(satnerf_fwd512g_kernel<AUXS, REND, SAVE>, "satnerf_fwd512g_kernel", kFwdWaves512, (size_t)kRing5 * 1024 + kFeat * sizeof(float4),
-                           REND ? kRendFloats : 0, p, st);
+  return launch_fwd_kernel(satnerf_fwd512g_kernel<AUXS, REND, SAVE, GEOM>, GEOM ? "satnerf_fwd512g_kernel (geometry)" : "satnerf_fwd512g_kernel",
+                           kFwdWaves512, (size_t)kRing5 * 1024 + kFeat * sizeof(float4), !REND ? 0 : GEOM ? kRendFloatsGeom : kRendFloats, p, st);
 }
 
 // entry of the 512-wide translation units: the generated core for inference, the render pass and the 8-bit training forward unless
@@ -179,6 +202,13 @@ int launch_fwd512_any(const FwdParams& p, int save_fmt, hipStream_t st) {
   if (route != FwdRoute::Core) return route == FwdRoute::Refused ? 1 : launch_fwd<1, AUXS>(p, save_fmt, st);
   if (save_fmt == SR_FMT8) return p.rend.rays != nullptr ? launch_fwd512g<AUXS, true, SR_FMT8>(p, st) : launch_fwd512g<AUXS, false, SR_FMT8>(p, st);
   return p.rend.rays != nullptr ? launch_fwd512g<AUXS, true>(p, st) : launch_fwd512g<AUXS, false>(p, st);
+}
+
+// entry of the 512-wide geometry translation units (mlp_fwd512g_g*.hip), as mlp_fwd2.inc launch_fwd_geom
+template <int AUXS>
+int launch_fwd512_geom(const FwdParams& p, hipStream_t st, int (*full)(const FwdParams&, int, hipStream_t)) {
+  if (fwd_route(p, 0, SR_FMT8, act8_units(AUXS), true) != FwdRoute::Core) return full(p, 0, st);
+  return p.rend.rays != nullptr ? launch_fwd512g<AUXS, true, 0, true>(p, st) : launch_fwd512g<AUXS, false, 0, true>(p, st);
 }
 
 #endif  // SR_FEAT == 512

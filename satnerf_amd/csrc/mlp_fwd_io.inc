@@ -3,7 +3,7 @@
 //   aux_values         the fp32 slot values of a lane's aux fragment(s), in front of the stream
 //   write_outputs      the output activations / the one-launch render and training epilogue behind the stream
 //   core_timing_store  the SR_CORE_TIMING experiment's three floats
-//   fwd_route          host: generated core, compiler-scheduled kernel (mlp_fwd.inc) or error, for the three launch_fwd*_any
+//   fwd_route          host (with mlp_params.h fwd_v1_forced): generated core, compiler-scheduled kernel (mlp_fwd.inc) or error, for the three launch_fwd*_any
 // The rest of the shell is in mlp_fwd.inc, beside the compiler-scheduled kernel that shares it (point_setup, aux_ws_bf16,
 // launch_fwd_kernel), and in mlp_device.h (uniform64).  NW = waves per workgroup (a workgroup's NW * 32 consecutive points are whole
 // rays under REND).
@@ -13,12 +13,6 @@
 #include "mlp_fwd.inc"
 
 namespace sr {
-
-// SATNERF_FWD_V1=1: every forward launch of the process runs the compiler-scheduled kernel (A/B against the generated cores)
-inline bool fwd_v1_forced() {
-  static const bool v1 = [] { const char* e = getenv("SATNERF_FWD_V1"); return e && e[0] == '1'; }();
-  return v1;
-}
 
 // Where a forward launch runs.  The generated core takes inference and its one native save format, while the stream's 32-bit workspace
 // offsets reach the whole workspace (tail waves included); everything else is the compiler-scheduled kernel's, which has no training
@@ -87,15 +81,36 @@ __device__ __forceinline__ void core_timing_store(const FwdParams& prm, long til
 // prm.train.target != NULL (the training forward, n_samples <= 64): wave w renders ray w, w + NW, ... of the workgroup AND takes the colour loss
 // and the compositing backward of that ray (render_loss_ray): the launch writes d_sigma / d_albedo / d_sun / g_beta / d_sky and one loss
 // partial per workgroup instead of weights / transparency -- what sr_ray_setup + this kernel + sr_render_loss did in three launches.
-constexpr int kRendFloats = 7;
-template <bool REND, int NW>
+// GEOM (the geometry cores, gen/fwd_core.py heads=False): `acc` is not read and sigma is the one per-point value.  REND then keeps
+// kRendFloatsGeom floats per point in LDS (depth, sigma) and each wave composites its rays sigma-only -- composite_ray with no albedo is
+// the reduction of the full render's depth / weights / transparency, in the same order -- with no sky head and no colour.
+constexpr int kRendFloats = 7, kRendFloatsGeom = 2;
+template <bool REND, int NW, bool GEOM = false>
 __device__ __forceinline__ void write_outputs(const FwdParams& prm, const PointIn& in, const f32x16& acc, float sig, float* r_z, int wave, int lane) {
   constexpr int P = NW * 32;
   float *r_sigma = r_z + P, *r_sun = r_z + 2 * P, *r_albedo = r_z + 3 * P, *r_beta = r_z + 6 * P;
   const int h = lane >> 5, pl = lane & 31;
   const long pt = in.pt, r = in.r, rg = in.rg;
   const bool valid = in.valid;
-  if constexpr (REND) {
+  if constexpr (GEOM && REND) {
+    const float sg = softplus_f(sig);
+    if (h == 0) {
+      r_sigma[wave * 32 + pl] = sg;
+      if (valid && prm.sigma) prm.sigma[pt] = sg;
+    }
+    __syncthreads();
+    const int S = prm.in.n_samples;
+    const int rays_here = P / S;  // host contract: S divides P
+    for (int lr = wave; lr < rays_here; lr += NW) {
+      const long ray = (long)blockIdx.x * rays_here + lr;
+      if (ray >= prm.rend.n_rays) break;
+      composite_ray(r_z + lr * S, r_sigma + lr * S, prm.rend.noise ? prm.rend.noise + ray * S : nullptr, prm.rend.noise_std, nullptr, nullptr, 0.f,
+                    0.f, 0.f, S, lane, 1, prm.rend.weights + ray * S, prm.rend.transp + ray * S, prm.rend.depth ? prm.rend.depth + ray : nullptr,
+                    nullptr);
+    }
+  } else if constexpr (GEOM) {
+    if (valid && h == 0 && prm.sigma) prm.sigma[pt] = softplus_f(sig);
+  } else if constexpr (REND) {
     const float sg = softplus_f(sig);
     if (h == 0) {
       r_sigma[wave * 32 + pl] = sg;

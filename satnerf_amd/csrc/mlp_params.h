@@ -1,6 +1,8 @@
 // Kernel parameter blocks shared by the API translation unit and the kernel instantiations (independent of the trunk width:
 // they stay outside the per-width inline namespace of mlp_layout.h).
 #pragma once
+#include <stdlib.h>
+
 #include "common.h"
 
 namespace sr {
@@ -10,6 +12,12 @@ namespace sr {
 constexpr int kFwdWaves256 = 8;     // width 256, bf16 / fp16 operands: two waves per SIMD
 constexpr int kFwdWavesParity = 4;  // width 256, parity mode: one wave per SIMD with the 512-register file
 constexpr int kFwdWaves512 = 4;     // width 512: likewise
+
+// SATNERF_FWD_V1=1: every forward launch of the process runs the compiler-scheduled kernel (A/B against the generated cores)
+inline bool fwd_v1_forced() {
+  static const bool v1 = [] { const char* e = getenv("SATNERF_FWD_V1"); return e && e[0] == '1'; }();
+  return v1;
+}
 
 // the fused render pass around the MLP (csrc/mlp_fwd.inc REND): stratified sampling in the prologue, the sky head and the
 // sigma->alpha compositing of the workgroup's rays in the epilogue.  rays == NULL: plain MLP launch.

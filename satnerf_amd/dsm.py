@@ -323,13 +323,20 @@ def dsm_from_clouds(east, north, alt, roi=None, resolution=0.5, mode="med", zone
                None if roi is None else tuple(float(v) for v in roi))
 
 
-def render_fused_dsm(models, views, args, center, scene_range, mode="med", **dsm_kwargs):
+def _rendered_depth(models, rays, ts, args, geometry_only):
+    """the per-ray depth of a whole image: from the full evaluation render, or (``geometry_only``) from the depth-only render
+    (``rendering.render_depth``: trunk and density only, one launch per pass)"""
+    from .rendering import render_depth, render_image_outputs
+
+    with torch.no_grad():
+        return (render_depth if geometry_only else render_image_outputs)(models, rays, ts, args)["depth"]
+
+
+def render_fused_dsm(models, views, args, center, scene_range, mode="med", geometry_only=False, **dsm_kwargs):
     """Render every view and fuse the clouds into one DSM: per ``(rays, ts)`` of ``views``, ``render_image_outputs(...)["depth"]`` ->
     ``ops.depth_to_utm`` -> :func:`dsm_from_clouds` (``dsm_kwargs``: roi, resolution).  The UTM zone is the first view's first
     point's and is handed to every later view, so a scene on a zone edge never mixes projections.  With ``roi=`` the result feeds
-    :func:`dsm_mae` unchanged."""
-    from .rendering import render_image_outputs
-
+    :func:`dsm_mae` unchanged.  ``geometry_only``: the depths come from ``rendering.render_depth`` (no colour, sun or uncertainty head)."""
     _check_mode(mode)
     views = list(views)
     if not views:
@@ -338,8 +345,7 @@ def render_fused_dsm(models, views, args, center, scene_range, mode="med", **dsm
     for rays, ts in views:
         if not (torch.is_tensor(rays) and rays.is_cuda):
             raise ValueError("rays must be GPU tensors: satnerf_amd has no CPU path")
-        with torch.no_grad():
-            depth = render_image_outputs(models, rays, ts, args)["depth"]
+        depth = _rendered_depth(models, rays, ts, args, geometry_only)
         rays32 = rays if rays.dtype == torch.float32 and rays.stride(-1) == 1 else rays.float().contiguous()
         east, north, alt, zone_out = ops.depth_to_utm(rays32, depth.reshape(-1).float().contiguous(), center, scene_range, number)
         if not number:
@@ -351,12 +357,10 @@ def render_fused_dsm(models, views, args, center, scene_range, mode="med", **dsm
     return dsm_from_clouds([c[0] for c in clouds], [c[1] for c in clouds], [c[2] for c in clouds], mode=mode, zone=zone_str, **dsm_kwargs)
 
 
-def render_dsm(models, rays, ts, args, center, scene_range, **dsm_kwargs):
-    """The create_satnerf_dsm flow in one call: ``render_image_outputs(...)["depth"]`` -> :func:`dsm_from_depth`."""
-    from .rendering import render_image_outputs
-
-    with torch.no_grad():
-        depth = render_image_outputs(models, rays, ts, args)["depth"]
+def render_dsm(models, rays, ts, args, center, scene_range, geometry_only=False, **dsm_kwargs):
+    """The create_satnerf_dsm flow in one call: ``render_image_outputs(...)["depth"]`` -> :func:`dsm_from_depth`.  ``geometry_only``:
+    the depth comes from ``rendering.render_depth`` instead (a DSM needs nothing else of the render)."""
+    depth = _rendered_depth(models, rays, ts, args, geometry_only)
     return dsm_from_depth(rays, depth, center, scene_range, **dsm_kwargs)
 
 
@@ -386,7 +390,7 @@ def _zone_of_center(center, device):
     return utm_zone(*torch.stack([lat[0], lon[0]]).cpu().tolist())
 
 
-def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, sun_d, roi=None, grid=None, zone=None):
+def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, sun_d, roi=None, grid=None, zone=None, geometry_only=False):
     """Render a nadir DSM of a trained field: ``data.ortho_rays`` over the grid -> ``render_image_outputs`` (once, no grad) ->
     :func:`ortho_dsm_from_depth`.  Every cell gets exactly one altitude, sampled along its own vertical, so the raster has no holes
     behind leaning buildings and involves no splat convention.
@@ -399,9 +403,9 @@ def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, su
     Returns (DSM, outputs).  ``outputs`` is the dict of ``render_image_outputs``; its per-ray tensors are in grid order, so
     ``outputs["rgb"].view(ysize, xsize, 3)`` is the true-ortho colour image, and likewise "albedo" (.., 3), "sun" (.., 1), "beta" (.., 1),
     "depth" / "acc" (ysize, xsize).  Cells outside the footprint the field was trained on are extrapolation: no footprint or visibility
-    mask is built."""
+    mask is built.  ``geometry_only``: the render is ``rendering.render_depth`` and ``outputs`` holds "depth" and "acc" only."""
     from .data import _ortho_grid, ortho_rays
-    from .rendering import render_image_outputs
+    from .rendering import render_depth, render_image_outputs
 
     if (roi is None) == (grid is None):
         raise ValueError("exactly one of roi= and grid= sizes the DSM")
@@ -423,5 +427,8 @@ def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, su
             ts = torch.full((n,), int(ts), dtype=torch.int64, device=dev)
         rays = ortho_rays(grid, zone, min_alt, max_alt, center, scene_range, sun_d, device=dev)
         with torch.no_grad():
-            outputs = render_image_outputs(models, rays, ts, args)
+            if geometry_only:
+                outputs = {k: v for k, v in render_depth(models, rays, ts, args).items() if k in ("depth", "acc")}
+            else:
+                outputs = render_image_outputs(models, rays, ts, args)
         return ortho_dsm_from_depth(outputs["depth"], grid, max_alt, scene_range, zone=str(zone), roi=roi), outputs

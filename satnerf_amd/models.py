@@ -284,6 +284,8 @@ class SatNeRF(_FlatParamModule):
         b = xyz.shape[0]
         if self.fused_forward(mode):
             hi, lo, l0 = self.packed(mode)
+            if sigma_only:  # models/satnerf.py:183-185: the trunk and the sigma row only (the full launch's sigma bit for bit)
+                return ops.satnerf_sigma(xyz, None, sun, None, t, None, b, 1, self.feat, self.t_embedding_dims, mode, hi, lo, l0).unsqueeze(1)
             albedo, sigma, sun_v, beta = ops.satnerf_mlp(xyz, None, sun, None, t, None, b, 1, self.feat, self.t_embedding_dims, mode, hi, lo, l0)
         else:
             from .generic import satnerf_points

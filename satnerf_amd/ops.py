@@ -173,11 +173,12 @@ def render_fused_ok(feat, mode, n_samples):
 
 
 def render_fwd(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_lo, l0, sky_w1, sky_b1, sky_w2, sky_b2, z=None, u=None, noise=None,
-               noise_std=0.0, seed=0, step_counter=None, tick=False, want_z=True, bank_chunks=0):
+               noise_std=0.0, seed=0, step_counter=None, tick=False, want_z=True, bank_chunks=0, want_sigma=False):
     """One launch: stratified sampling (or given depths ``z``) -> fused MLP -> sky head + compositing (sr_satnerf_render_fwd).
     Depths: ``z`` (N,S) given, else stratified with ``u`` (N,S), else jitter drawn in the kernel (``seed``, ``step_counter``, ``tick``).
     ``bank_chunks`` > 0: ``rays`` / ``ts`` are a bank of bank_chunks x N rows and the launch renders chunk step_counter[0] % bank_chunks.
-    Returns dict(z, albedo (N,S,3), sun_v (N,S), beta (N,S), sky (N,3), weights, transparency (N,S), depth (N), rgb (N,3))."""
+    Returns dict(z, albedo (N,S,3), sun_v (N,S), beta (N,S), sky (N,3), weights, transparency (N,S), depth (N), rgb (N,3)), and
+    ``sigma`` (N,S) with ``want_sigma``."""
     rays, stride = _rows(rays, "rays", 11)
     n, s, dev = rays.shape[0], int(n_samples), rays.device
     if bank_chunks:
@@ -193,14 +194,70 @@ def render_fwd(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_lo,
     e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
     out = {"z": z if z is not None else (e(n, s) if want_z else None), "albedo": e(n, s, 3), "sun_v": e(n, s), "beta": e(n, s), "sky": e(n, 3),
            "weights": e(n, s), "transparency": e(n, s), "depth": e(n), "rgb": e(n, 3)}
+    if want_sigma:
+        out["sigma"] = e(n, s)
     args = _lib.RenderArgs(_p(rays), stride, _p(ts), _p(temb), n, s, _p(z), _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
                            _p(_chk(step_counter, "step_counter", allow_none=True)), int(bool(tick)), _p(noise), float(noise_std), sky_w1.shape[0],
                            _p(_chk(sky_w1, "w1")), _p(_chk(sky_b1, "b1")), _p(_chk(sky_w2, "w2")), _p(_chk(sky_b2, "b2")), int(bank_chunks))
-    outs = _lib.RenderOutputs(_p(out["z"]) if z is None else None, _p(out["albedo"]), None, _p(out["sun_v"]), _p(out["beta"]), _p(out["sky"]),
-                              _p(out["weights"]), _p(out["transparency"]), _p(out["depth"]), _p(out["rgb"]))
+    outs = _lib.RenderOutputs(_p(out["z"]) if z is None else None, _p(out["albedo"]), _p(out.get("sigma")), _p(out["sun_v"]), _p(out["beta"]),
+                              _p(out["sky"]), _p(out["weights"]), _p(out["transparency"]), _p(out["depth"]), _p(out["rgb"]))
     with _timed("mlp_fwd"):
         _lib.call("sr_satnerf_render_fwd", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs), _stream())
     return out
+
+
+def render_depth(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_lo, l0, sky=None, z=None, u=None, noise=None, noise_std=0.0, seed=0,
+                 step_counter=None, tick=False, want_z=True, want_sigma=False):
+    """The depth-only render pass in one launch (sr_satnerf_render_depth): ``render_fwd``'s sampling and inputs, the trunk and the sigma
+    row of the same packed stream, sigma-only compositing -- no colour, sun, uncertainty or sky weight is read in the ``bf16`` / ``f16``
+    modes.  ``sky`` = (w1, b1, w2, b2) or None: only the configurations the full kernel serves (``bf16x3``, SATNERF_FWD_V1=1) need it.
+    ``n_samples`` must divide the points of a workgroup (``render_fused_ok``); otherwise the C entry's error is raised.
+    Returns dict(z (N,S) or None, sigma (N,S) or None, weights, transparency (N,S), depth (N)): ``render_fwd``'s values bit for bit."""
+    rays, stride = _rows(rays, "rays", 11)
+    n, s, dev = rays.shape[0], int(n_samples), rays.device
+    _chk(ts, "ts", torch.int64), _chk(temb, "temb")
+    for t, nm in ((z, "z"), (u, "u"), (noise, "noise")):
+        if t is not None and tuple(_chk(t, nm).shape) != (n, s):
+            raise ValueError(f"{nm} must be ({n},{s}), got {tuple(t.shape)}")
+    if tick and (step_counter is None or step_counter.numel() < 4):
+        raise ValueError("tick=True needs step_counter = a zero-initialised float32 block of 4")
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"z": z if z is not None else (e(n, s) if want_z else None), "sigma": e(n, s) if want_sigma else None, "weights": e(n, s),
+           "transparency": e(n, s), "depth": e(n)}
+    if n == 0:
+        return out
+    w = [None] * 4 if sky is None else [_chk(t, nm) for t, nm in zip(sky, ("w1", "b1", "w2", "b2"))]
+    args = _lib.RenderArgs(_p(rays), stride, _p(ts), _p(temb), n, s, _p(z), _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           _p(_chk(step_counter, "step_counter", allow_none=True)), int(bool(tick)), _p(noise), float(noise_std),
+                           0 if sky is None else w[0].shape[0], _p(w[0]), _p(w[1]), _p(w[2]), _p(w[3]), 0)
+    outs = _lib.RenderOutputs(_p(out["z"]) if z is None else None, None, _p(out["sigma"]), None, None, None, _p(out["weights"]),
+                              _p(out["transparency"]), _p(out["depth"]), None)
+    with _timed("mlp_fwd"):
+        _lib.call("sr_satnerf_render_depth", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs),
+                  _stream())
+    return out
+
+
+def satnerf_sigma(org, direction, sun, z, temb, ts, n_points, n_samples, feat, tau, mode, stream_hi, stream_lo, l0):
+    """sigma (P,) of the fused MLP over n_points sample points (sr_satnerf_mlp_sigma): ``satnerf_mlp``'s arguments and its sigma bit for
+    bit, from the trunk-and-sigma core -- the heads are not evaluated."""
+    org, so = _rows(org, "org", 3)
+    sun, ss = _rows(sun, "sun", 3)
+    sd = 0
+    if direction is not None:
+        direction, sd = _rows(direction, "dir", 3)
+    if z is not None:
+        _chk(z, "z")
+    _chk(temb, "temb")
+    if ts is not None:
+        _chk(ts, "ts", torch.int64)
+    sigma = torch.empty(n_points, dtype=torch.float32, device=org.device)
+    if n_points == 0:
+        return sigma
+    inp = _lib.MlpInputs(_p(org), so, _p(direction), sd, _p(sun), ss, _p(z), _p(temb), _p(ts), n_points, n_samples)
+    with _timed("mlp_fwd"):
+        _lib.call("sr_satnerf_mlp_sigma", C.byref(inp), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), _p(sigma), _stream())
+    return sigma
 
 
 def render_train(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_lo, l0, sky_w1, sky_b1, sky_w2, sky_b2, target, acts, u=None,

@@ -103,6 +103,35 @@ def kernel_rng(seed, counter, bank_chunks=0):
         _rng = prev
 
 
+class _RecordRng:
+    """Passes the draws of the generator in force through and keeps the uniform ones (``render_depth`` rebuilds the depths of a
+    ``render_rays`` chunk from them)."""
+
+    def __init__(self, inner):
+        self.inner, self.rands = inner, []
+
+    def rand(self, n, m, device):
+        self.rands.append(self.inner.rand(n, m, device))
+        return self.rands[-1]
+
+    def randn(self, n, m, device):
+        return self.inner.randn(n, m, device)
+
+
+@contextlib.contextmanager
+def _recorded_rands(enabled):
+    global _rng
+    if not enabled:
+        yield None
+        return
+    # (jitter drawn inside a kernel cannot be kept: under kernel_rng these chunks draw it from torch's generator on the host instead)
+    prev, _rng = _rng, _RecordRng(_TorchRng() if isinstance(_rng, _KernelRng) else _rng)
+    try:
+        yield _rng.rands
+    finally:
+        _rng = prev
+
+
 @contextlib.contextmanager
 def replay_rng(draws):
     """Feed ``render_rays`` a recorded list of random tensors instead of fresh draws (parity tests)."""
@@ -411,6 +440,92 @@ def render_image_outputs(models, rays, ts, args):
     out = {k: image[:, a:b] for k, (a, b) in ops.IMAGE_COLUMNS.items()}
     out["depth"], out["acc"] = out["depth"][:, 0], out["acc"][:, 0]
     out["typ"] = typ
+    return out
+
+
+@torch.no_grad()
+def render_depth(models, rays, ts, args, return_weights=False):
+    """Depth-only ("geometry") rendering of a whole image, the cut the reference's model offers as ``sigma_only`` (models/satnerf.py:183-185)
+    carried through the render: rays -> ``{"typ", "depth" (N,), "acc" (N,)}`` of the finest model present, plus ``"weights"``,
+    ``"transparency"`` and ``"z"`` (N,S) with ``return_weights``; chunked by ``args.chunk``.
+
+    Where the model runs the fused kernel in ``bf16`` / ``f16`` and the sample count divides a workgroup's points, each pass is ONE
+    launch of the trunk-and-sigma core (``ops.render_depth``): no colour, sun-visibility, uncertainty or sky weight is read and no
+    per-point value leaves the kernel.  With ``n_importance > 0``: coarse depth-only pass -> ``ops.sample_pdf_merge`` -> fine depth-only
+    pass on the merged depths.  Everything else (the classic ``nerf``, other widths, ``bf16x3``, other sample counts) renders through
+    ``render_rays`` and returns the same keys; s-nerf rides on the Sat-NeRF kernels (``_as_satnerf``).
+
+    Random draws per chunk are ``render_rays``' in order and shape -- the noise of the passes skipped here (solar correction) included --
+    so a seed (or ``replay_rng``) gives the depths of the full render: bit for bit, as sigma's arithmetic and the compositing reduction
+    are the full kernel's."""
+    if args.model not in ("sat-nerf", "s-nerf", "nerf"):
+        raise ValueError(f"model {args.model} is not valid")
+    if not rays.is_cuda:
+        raise RuntimeError("rays must be on the GPU: satnerf_amd has no CPU path")
+    if args.model == "s-nerf":
+        models, args = _as_satnerf(models, args)
+        ts = torch.zeros(rays.shape[0], dtype=torch.int64, device=rays.device)
+    elif args.model == "sat-nerf":
+        if ts is None:
+            raise TypeError("sat-nerf needs per-ray image indices ts")
+        validate_ts(ts, models)
+    n_total, s, n_imp, dev = rays.shape[0], args.n_samples, args.n_importance, rays.device
+    typ = "fine" if n_imp > 0 else "coarse"
+    mode = _mode_of(args)
+    s_out = s + n_imp
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"typ": typ, "depth": e(n_total), "acc": e(n_total)}
+    if return_weights:
+        out.update(weights=e(n_total, s_out), transparency=e(n_total, s_out), z=e(n_total, s_out))
+
+    def geometry_ok(model, k):
+        return (_FUSED_RENDER and mode in ("bf16", "f16") and hasattr(model, "fused_forward") and hasattr(model, "t_embedding_dims") and model.fused_forward(mode)
+                and ops.render_fused_ok(model.feat, mode, k))
+
+    fused = args.model != "nerf" and geometry_ok(models["coarse"], s) and (n_imp == 0 or geometry_ok(models["fine"], s_out))
+    kernel = isinstance(_rng, _KernelRng)
+    if kernel and _rng.bank_chunks:
+        raise NotImplementedError("render_depth renders the rays it is given, chunk by chunk: a bank-walking kernel_rng is render_rays'")
+    skip_noise = kernel and args.noise_std == 0
+    use_noise = args.noise_std != 0
+    if fused:
+        emb = (models["t"].weight.data if hasattr(models["t"], "weight") else models["t"]).contiguous().float()
+
+    def one_pass(model, r, t, z_cur, u_cur, k, want_z):
+        n = r.shape[0]
+        noise = None if skip_noise else _rng.randn(n, k, dev)  # models/satnerf.py:58 -- always drawn
+        hi, lo, l0 = model.packed(mode)
+        sk = model.sky_color  # (read only where the full kernel serves the request: SATNERF_FWD_V1=1)
+        draw = z_cur is None and u_cur is None
+        o = ops.render_depth(r, t, emb, k, model.feat, model.t_embedding_dims, mode, hi, lo, l0,
+                             sky=(sk[0].weight.data, sk[0].bias.data, sk[2].weight.data, sk[2].bias.data), z=z_cur, u=u_cur,
+                             noise=noise if use_noise else None, noise_std=args.noise_std, seed=_rng.seed if draw else 0,
+                             step_counter=_rng.counter if draw else None, tick=draw, want_z=want_z)
+        if args.sc_lambda > 0 and not skip_noise:
+            _rng.randn(n, k, dev)  # the solar-correction pass of render_rays draws here; it has no part in the depth
+        return o
+
+    for i in range(0, n_total, args.chunk):
+        r = rays[i:i + args.chunk].contiguous().float()
+        n = r.shape[0]
+        if not fused:
+            with _recorded_rands(return_weights) as rands:
+                res = render_rays(models, args, r, None if ts is None else ts[i:i + args.chunk], _ts_validated=True)
+            o = {"depth": res[f"depth_{typ}"], "weights": res[f"weights_{typ}"], "transparency": res[f"transparency_{typ}"]}
+            if return_weights:  # render_rays does not return its depths: they are rebuilt from its uniform draws (rendering.py:62-78,118-121)
+                o["z"] = ops.ray_sample(r, rands[0], s)
+                if n_imp > 0:
+                    o["z"] = ops.sample_pdf_merge(o["z"], res["weights_coarse"], rands[1])
+        else:
+            t = ts[i:i + args.chunk].contiguous().long().view(-1)
+            o = one_pass(models["coarse"], r, t, None, None if kernel else _rng.rand(n, s, dev), s, n_imp > 0 or return_weights)
+            if n_imp > 0:
+                z_fine = ops.sample_pdf_merge(o["z"], o["weights"], _rng.rand(n, n_imp, dev))
+                o = one_pass(models["fine"], r, t, z_fine, None, s_out, True)
+        out["depth"][i:i + n] = o["depth"]
+        torch.sum(o["weights"], -1, out=out["acc"][i:i + n])
+        if return_weights:
+            out["weights"][i:i + n], out["transparency"][i:i + n], out["z"][i:i + n] = o["weights"], o["transparency"], o["z"]
     return out
 
 
