@@ -3,8 +3,6 @@
 #define SR_F16 1
 #include "mlp_fwd512g.inc"
 namespace sr {
-int launch_fwd512_h1a1(const FwdParams&, int, hipStream_t);
-int launch_fwd512_h1a2(const FwdParams&, int, hipStream_t);
 int launch_fwd512_geom_h1a1(const FwdParams& p, hipStream_t st) { return launch_fwd512_geom<1>(p, st, launch_fwd512_h1a1); }
 int launch_fwd512_geom_h1a2(const FwdParams& p, hipStream_t st) { return launch_fwd512_geom<2>(p, st, launch_fwd512_h1a2); }
 }  // namespace sr

@@ -82,6 +82,31 @@ struct FwdParams {
   int tau;
 };
 
+// ---- the launchers of the per-variant translation units, declared here alone; mlp_api.hip's table kFwdUnits is what chooses among them.
+// p = bf16 operands, h = fp16 (SR_MODE_F16), p3 = parity (SR_MODE_BF16X3); a1 / a2 = aux steps (mlp_layout.h aux_steps(tau))
+using FwdLaunch = int (*)(const FwdParams&, int save_fmt, hipStream_t);  // a unit's whole kernel (mlp_fwd*_{p1,p3,h1}a*.hip)
+using FwdGeomLaunch = int (*)(const FwdParams&, hipStream_t);           // its trunk-and-sigma build (mlp_fwdg_*.hip, mlp_fwd512g_g*.hip)
+int launch_fwd_p1a1(const FwdParams&, int, hipStream_t);
+int launch_fwd_p1a2(const FwdParams&, int, hipStream_t);
+int launch_fwd_h1a1(const FwdParams&, int, hipStream_t);
+int launch_fwd_h1a2(const FwdParams&, int, hipStream_t);
+int launch_fwd_p3a1(const FwdParams&, int, hipStream_t);
+int launch_fwd_p3a2(const FwdParams&, int, hipStream_t);
+int launch_fwd512_p1a1(const FwdParams&, int, hipStream_t);
+int launch_fwd512_p1a2(const FwdParams&, int, hipStream_t);
+int launch_fwd512_h1a1(const FwdParams&, int, hipStream_t);
+int launch_fwd512_h1a2(const FwdParams&, int, hipStream_t);
+int launch_fwd_geom_p1a1(const FwdParams&, hipStream_t);
+int launch_fwd_geom_p1a2(const FwdParams&, hipStream_t);
+int launch_fwd_geom_h1a1(const FwdParams&, hipStream_t);
+int launch_fwd_geom_h1a2(const FwdParams&, hipStream_t);
+int launch_fwd512_geom_p1a1(const FwdParams&, hipStream_t);
+int launch_fwd512_geom_p1a2(const FwdParams&, hipStream_t);
+int launch_fwd512_geom_h1a1(const FwdParams&, hipStream_t);
+int launch_fwd512_geom_h1a2(const FwdParams&, hipStream_t);
+long fwd512_stream_pieces_a1();  // FwdStream<AUXS>::total_pieces() of the 512-wide layout (mlp_fwd512_p1a*.hip)
+long fwd512_stream_pieces_a2();
+
 struct BwdParams {
   const float* g_albedo;  // upstream gradients of the per-point outputs (any may be null = 0)
   const float* g_sigma;

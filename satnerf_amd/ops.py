@@ -141,9 +141,8 @@ def sky(sun, w1, b1, w2, b2):
     return out
 
 
-def satnerf_mlp(org, direction, sun, z, temb, ts, n_points, n_samples, feat, tau, mode, stream_hi, stream_lo, l0, acts=None, fmt=16):
-    """Fused MLP over n_points sample points; returns (albedo (P,3), sigma (P), sun_v (P), beta (P)).  ``acts`` = training
-    workspace (``acts_workspace(..., fmt)``) the activations are saved to in format ``fmt`` (16 | 8)."""
+def _mlp_inputs(org, direction, sun, z, temb, ts, n_points, n_samples):
+    """The sr_mlp_inputs block of a point launch, its tensors validated (``org`` / ``direction`` / ``sun`` may be strided rows)."""
     org, so = _rows(org, "org", 3)
     sun, ss = _rows(sun, "sun", 3)
     sd = 0
@@ -154,12 +153,42 @@ def satnerf_mlp(org, direction, sun, z, temb, ts, n_points, n_samples, feat, tau
     _chk(temb, "temb")
     if ts is not None:
         _chk(ts, "ts", torch.int64)
+    return _lib.MlpInputs(_p(org), so, _p(direction), sd, _p(sun), ss, _p(z), _p(temb), _p(ts), n_points, n_samples)
+
+
+def _render_args(rays, ts, temb, n_samples, sky, z, u, noise, noise_std, seed, step_counter, tick, bank_chunks=0, n=None):
+    """The sr_render_args block of a render launch over ``n`` rays (default: the rows of ``rays``), its tensors validated; ``sky`` =
+    (w1, b1, w2, b2) or None.  Returns (args, n, n_samples, an allocator of fp32 tensors on the rays' device)."""
+    rays, stride = _rows(rays, "rays", 11)
+    n, s = rays.shape[0] if n is None else n, int(n_samples)
+    _chk(ts, "ts", torch.int64), _chk(temb, "temb")
+    for t, nm in ((z, "z"), (u, "u"), (noise, "noise")):
+        if t is not None and tuple(_chk(t, nm).shape) != (n, s):
+            raise ValueError(f"{nm} must be ({n},{s}), got {tuple(t.shape)}")
+    if tick and (step_counter is None or step_counter.numel() < 4):
+        raise ValueError("tick=True needs step_counter = a zero-initialised float32 block of 4")
+    w = [None] * 4 if sky is None else [_chk(t, nm) for t, nm in zip(sky, ("w1", "b1", "w2", "b2"))]
+    args = _lib.RenderArgs(_p(rays), stride, _p(ts), _p(temb), n, s, _p(z), _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           _p(_chk(step_counter, "step_counter", allow_none=True)), int(tick), _p(noise), float(noise_std),
+                           0 if sky is None else w[0].shape[0], *map(_p, w), int(bank_chunks))
+    return args, n, s, lambda *shape: torch.empty(*shape, dtype=torch.float32, device=rays.device)
+
+
+def _render_outputs(out, z=None):
+    """The sr_render_outputs block of a wrapper's result dict: an absent or None entry is not written, nor are given depths ``z``."""
+    return _lib.RenderOutputs(None if z is not None else _p(out.get("z")),
+                              *(_p(out.get(k)) for k in ("albedo", "sigma", "sun_v", "beta", "sky", "weights", "transparency", "depth", "rgb")))
+
+
+def satnerf_mlp(org, direction, sun, z, temb, ts, n_points, n_samples, feat, tau, mode, stream_hi, stream_lo, l0, acts=None, fmt=16):
+    """Fused MLP over n_points sample points; returns (albedo (P,3), sigma (P), sun_v (P), beta (P)).  ``acts`` = training
+    workspace (``acts_workspace(..., fmt)``) the activations are saved to in format ``fmt`` (16 | 8)."""
+    inp = _mlp_inputs(org, direction, sun, z, temb, ts, n_points, n_samples)
     dev = org.device
     albedo = torch.empty(n_points, 3, dtype=torch.float32, device=dev)
     sigma = torch.empty(n_points, dtype=torch.float32, device=dev)
     sun_v = torch.empty(n_points, dtype=torch.float32, device=dev)
     beta = torch.empty(n_points, dtype=torch.float32, device=dev)
-    inp = _lib.MlpInputs(_p(org), so, _p(direction), sd, _p(sun), ss, _p(z), _p(temb), _p(ts), n_points, n_samples)
     with _timed("mlp_fwd"):
         _lib.call("sr_satnerf_mlp_fwd", C.byref(inp), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), _p(albedo), _p(sigma),
                   _p(sun_v), _p(beta), _p(acts), int(fmt), _stream())
@@ -179,28 +208,18 @@ def render_fwd(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_lo,
     ``bank_chunks`` > 0: ``rays`` / ``ts`` are a bank of bank_chunks x N rows and the launch renders chunk step_counter[0] % bank_chunks.
     Returns dict(z, albedo (N,S,3), sun_v (N,S), beta (N,S), sky (N,3), weights, transparency (N,S), depth (N), rgb (N,3)), and
     ``sigma`` (N,S) with ``want_sigma``."""
-    rays, stride = _rows(rays, "rays", 11)
-    n, s, dev = rays.shape[0], int(n_samples), rays.device
+    n = None
     if bank_chunks:
         if rays.shape[0] % bank_chunks or ts.numel() != rays.shape[0] or step_counter is None:
             raise ValueError("bank mode: rays / ts must hold bank_chunks x N rows and step_counter is required")
         n = rays.shape[0] // bank_chunks
-    _chk(ts, "ts", torch.int64), _chk(temb, "temb")
-    for t, nm in ((z, "z"), (u, "u"), (noise, "noise")):
-        if t is not None and tuple(_chk(t, nm).shape) != (n, s):
-            raise ValueError(f"{nm} must be ({n},{s}), got {tuple(t.shape)}")
-    if tick and (step_counter is None or step_counter.numel() < 4):
-        raise ValueError("tick=True needs step_counter = a zero-initialised float32 block of 4")
-    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    args, n, s, e = _render_args(rays, ts, temb, n_samples, (sky_w1, sky_b1, sky_w2, sky_b2), z, u, noise, noise_std, seed, step_counter, bool(tick),
+                                 bank_chunks, n)
     out = {"z": z if z is not None else (e(n, s) if want_z else None), "albedo": e(n, s, 3), "sun_v": e(n, s), "beta": e(n, s), "sky": e(n, 3),
            "weights": e(n, s), "transparency": e(n, s), "depth": e(n), "rgb": e(n, 3)}
     if want_sigma:
         out["sigma"] = e(n, s)
-    args = _lib.RenderArgs(_p(rays), stride, _p(ts), _p(temb), n, s, _p(z), _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                           _p(_chk(step_counter, "step_counter", allow_none=True)), int(bool(tick)), _p(noise), float(noise_std), sky_w1.shape[0],
-                           _p(_chk(sky_w1, "w1")), _p(_chk(sky_b1, "b1")), _p(_chk(sky_w2, "w2")), _p(_chk(sky_b2, "b2")), int(bank_chunks))
-    outs = _lib.RenderOutputs(_p(out["z"]) if z is None else None, _p(out["albedo"]), _p(out.get("sigma")), _p(out["sun_v"]), _p(out["beta"]),
-                              _p(out["sky"]), _p(out["weights"]), _p(out["transparency"]), _p(out["depth"]), _p(out["rgb"]))
+    outs = _render_outputs(out, z)
     with _timed("mlp_fwd"):
         _lib.call("sr_satnerf_render_fwd", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs), _stream())
     return out
@@ -213,25 +232,12 @@ def render_depth(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_l
     modes.  ``sky`` = (w1, b1, w2, b2) or None: only the configurations the full kernel serves (``bf16x3``, SATNERF_FWD_V1=1) need it.
     ``n_samples`` must divide the points of a workgroup (``render_fused_ok``); otherwise the C entry's error is raised.
     Returns dict(z (N,S) or None, sigma (N,S) or None, weights, transparency (N,S), depth (N)): ``render_fwd``'s values bit for bit."""
-    rays, stride = _rows(rays, "rays", 11)
-    n, s, dev = rays.shape[0], int(n_samples), rays.device
-    _chk(ts, "ts", torch.int64), _chk(temb, "temb")
-    for t, nm in ((z, "z"), (u, "u"), (noise, "noise")):
-        if t is not None and tuple(_chk(t, nm).shape) != (n, s):
-            raise ValueError(f"{nm} must be ({n},{s}), got {tuple(t.shape)}")
-    if tick and (step_counter is None or step_counter.numel() < 4):
-        raise ValueError("tick=True needs step_counter = a zero-initialised float32 block of 4")
-    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    args, n, s, e = _render_args(rays, ts, temb, n_samples, sky, z, u, noise, noise_std, seed, step_counter, bool(tick))
     out = {"z": z if z is not None else (e(n, s) if want_z else None), "sigma": e(n, s) if want_sigma else None, "weights": e(n, s),
            "transparency": e(n, s), "depth": e(n)}
     if n == 0:
         return out
-    w = [None] * 4 if sky is None else [_chk(t, nm) for t, nm in zip(sky, ("w1", "b1", "w2", "b2"))]
-    args = _lib.RenderArgs(_p(rays), stride, _p(ts), _p(temb), n, s, _p(z), _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                           _p(_chk(step_counter, "step_counter", allow_none=True)), int(bool(tick)), _p(noise), float(noise_std),
-                           0 if sky is None else w[0].shape[0], _p(w[0]), _p(w[1]), _p(w[2]), _p(w[3]), 0)
-    outs = _lib.RenderOutputs(_p(out["z"]) if z is None else None, None, _p(out["sigma"]), None, None, None, _p(out["weights"]),
-                              _p(out["transparency"]), _p(out["depth"]), None)
+    outs = _render_outputs(out, z)
     with _timed("mlp_fwd"):
         _lib.call("sr_satnerf_render_depth", C.byref(args), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), C.byref(outs),
                   _stream())
@@ -241,20 +247,10 @@ def render_depth(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_l
 def satnerf_sigma(org, direction, sun, z, temb, ts, n_points, n_samples, feat, tau, mode, stream_hi, stream_lo, l0):
     """sigma (P,) of the fused MLP over n_points sample points (sr_satnerf_mlp_sigma): ``satnerf_mlp``'s arguments and its sigma bit for
     bit, from the trunk-and-sigma core -- the heads are not evaluated."""
-    org, so = _rows(org, "org", 3)
-    sun, ss = _rows(sun, "sun", 3)
-    sd = 0
-    if direction is not None:
-        direction, sd = _rows(direction, "dir", 3)
-    if z is not None:
-        _chk(z, "z")
-    _chk(temb, "temb")
-    if ts is not None:
-        _chk(ts, "ts", torch.int64)
+    inp = _mlp_inputs(org, direction, sun, z, temb, ts, n_points, n_samples)
     sigma = torch.empty(n_points, dtype=torch.float32, device=org.device)
     if n_points == 0:
         return sigma
-    inp = _lib.MlpInputs(_p(org), so, _p(direction), sd, _p(sun), ss, _p(z), _p(temb), _p(ts), n_points, n_samples)
     with _timed("mlp_fwd"):
         _lib.call("sr_satnerf_mlp_sigma", C.byref(inp), feat, tau, MODES[mode], _p(stream_hi), _p(stream_lo), _p(_chk(l0, "l0")), _p(sigma), _stream())
     return sigma
@@ -269,30 +265,21 @@ def render_train(rays, ts, temb, n_samples, feat, tau, mode, stream_hi, stream_l
     return, bit for bit.  ``tick`` = 2: the launch opens the step (advances ``step_counter`` and draws for the advanced value).
     ``gather`` = dict(idx, cursor, batches, out=(rays (N,11), rgbs (N,3), ts (N))): ``rays`` / ``ts`` / ``target`` are the resident bank and
     the launch samples batch cursor[0] of the epoch's shuffled ``idx`` itself, writing the batch rows to ``out``."""
-    rays, stride = _rows(rays, "rays", 11)
-    n, s, dev = rays.shape[0], int(n_samples), rays.device
+    args, n, s, e = _render_args(rays, ts, temb, n_samples, (sky_w1, sky_b1, sky_w2, sky_b2), None, u, noise, noise_std, seed, step_counter, tick,
+                                 n=None if gather is None else gather["out"][0].shape[0])
     if gather is not None:
         o_rays, o_rgbs, o_ts = gather["out"]
-        n = o_rays.shape[0]
-        if (stride != 11 or tuple(_chk(o_rays, "out rays").shape) != (n, 11) or tuple(_chk(o_rgbs, "out rgbs").shape) != (n, 3)
+        if (args.ray_stride != 11 or tuple(_chk(o_rays, "out rays").shape) != (n, 11) or tuple(_chk(o_rgbs, "out rgbs").shape) != (n, 3)
                 or tuple(_chk(o_ts, "out ts", torch.int64).shape) != (n,) or _chk(gather["idx"], "idx", torch.int64).numel() < int(gather["batches"]) * n
                 or target.shape[0] != rays.shape[0] or ts.shape[0] != rays.shape[0] or u is not None or noise is not None):
             raise ValueError("gather: the bank (rays (R,11), ts (R), target (R,3)), idx (>= batches x N) and out = ((N,11), (N,3), (N,)) do not fit")
-    _chk(ts, "ts", torch.int64), _chk(temb, "temb")
-    for t, nm in ((u, "u"), (noise, "noise")):
-        if t is not None and tuple(_chk(t, nm).shape) != (n, s):
-            raise ValueError(f"{nm} must be ({n},{s}), got {tuple(t.shape)}")
     per_block = _lib.lib().sr_render_points_per_block(int(feat), MODES[mode])
     if per_block <= 0 or s > 64 or per_block % s:
         raise ValueError(f"no fused training forward for feat={feat}, mode={mode}, n_samples={s}")
-    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-    out = {"z": e(n, s) if want_z else None, "albedo": e(n, s, 3), "sigma": e(n, s), "sun_v": e(n, s), "beta": e(n, s), "sky": e(n, 3),
-           "loss": e((n * s + per_block - 1) // per_block), "rgb": e(n, 3), "d_sigma": e(n, s), "d_albedo": e(n, s, 3), "d_sun": e(n, s),
-           "g_beta": e(n, s), "d_sky": e(n, 3)}
-    args = _lib.RenderArgs(_p(rays), stride, _p(ts), _p(temb), n, s, None, _p(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                           _p(_chk(step_counter, "step_counter", allow_none=True)), int(tick), _p(noise), float(noise_std), sky_w1.shape[0],
-                           _p(_chk(sky_w1, "w1")), _p(_chk(sky_b1, "b1")), _p(_chk(sky_w2, "w2")), _p(_chk(sky_b2, "b2")), 0)
-    outs = _lib.RenderOutputs(_p(out["z"]), _p(out["albedo"]), _p(out["sigma"]), _p(out["sun_v"]), _p(out["beta"]), _p(out["sky"]), None, None, None, None)
+    out = {"z": e(n, s) if want_z else None, "albedo": e(n, s, 3), "sigma": e(n, s), "sun_v": e(n, s), "beta": e(n, s), "sky": e(n, 3)}
+    outs = _render_outputs(out)  # the launch writes what follows through sr_train_args
+    out.update({"loss": e((n * s + per_block - 1) // per_block), "rgb": e(n, 3), "d_sigma": e(n, s), "d_albedo": e(n, s, 3), "d_sun": e(n, s),
+                "g_beta": e(n, s), "d_sky": e(n, 3)})
     g = gather or {}
     tr = _lib.TrainArgs(_p(_chk(target, "target")), _p(_chk(sched, "sched", allow_none=True)), float(beta_min), _p(out["loss"]), _p(out["rgb"]),
                         _p(out["d_sigma"]), _p(out["d_albedo"]), _p(out["d_sun"]), _p(out["g_beta"]), _p(out["d_sky"]),
