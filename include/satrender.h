@@ -578,6 +578,35 @@ int sr_utm_to_latlon(const double* east, const double* north, int64_t n, int zon
 int sr_ortho_rays(double xoff, double yoff, double resolution, int xsize, int ysize, int zone, double min_alt, double max_alt,
                   const double* center, double range, const float* sun_d, float* rays, int row_stride, double* latlon, void* stream);
 
+/* ---- geometric sun visibility: the ray from a rendered surface point towards the sun ---------------------------
+ * The solar correction (metrics.py:27-33) trains the sun_v head towards the transparency the density leaves along a ray towards the
+ * sun.  The reference's own sun rays (the `sc` pass, rendering.py:102-108) cannot serve to compute it: they add the east / north / up
+ * vector of rays[:, 8:11] to an ECEF origin (a mixed frame) and start at the camera ray's origin, not at the surface.  sr_sun_rays
+ * writes that ray in the scene's normalised ECEF frame; rendering it with sr_satnerf_render_depth and keeping the transparency in
+ * front of the last sample (models/satnerf.py:52-63, column -1) gives the visibility; sr_sun_shade relights with it.
+ * sr_sun_rays, per primary ray i: r = row i of rays (DEVICE fp32, ray_stride >= 11), t = depth[i] (DEVICE fp32), s = sun_d (3 HOST
+ * floats: the call's one sun vector) or, with sun_d NULL, r[8..10]; s is (east, north, up) and need not be a unit vector.  In fp64
+ * with contraction off, rounded to fp32 once:
+ *   s^ = s / |s|;  P = o + d t;  E = P range + center (`center` = 3 HOST doubles);  (phi, lambda, alt) = sr_latlonalt_from_depth's
+ *   dir  = s^_e e + s^_n n + s^_u u,  e = (-sin l, cos l, 0), n = (-sin p cos l, -sin p sin l, cos p), u = (cos p cos l, cos p sin l, sin p)
+ *   L    = (max_alt - alt) / (s^_u range): where the ray reaches max_alt (metres) on the local tangent plane
+ *   near = bias_abs + bias_rel (r[7] - r[6]), far = max(near, L); the bias keeps the ray from starting inside the surface it leaves
+ * Row i of out (DEVICE fp32, out_stride >= 11, columns beyond 10 untouched) = [P(3) dir(3) near far sun(3)], sun = r[8..10] unchanged or
+ * the call's sun_d as given (not normalised).  A ray is invalid when t or E is not finite, |s| is zero or not finite, or s^_u <= 0:
+ * valid[i] (DEVICE uint8) = 0 and the row is [o(3) d(3) 0 0 sun(3)], a finite zero-length ray; otherwise valid[i] = 1.  latlonalt
+ * ((3, n) DEVICE fp64: lat, lon in degrees, alt in metres; may be NULL) holds sr_latlonalt_from_depth's values bit for bit.  out
+ * must not overlap rays.  Errors (nothing is launched): a stride < 11, range not finite or <= 0, max_alt or center not finite, a bias
+ * negative or not finite, a call-level sun_d that is not finite, zero or has up <= 0, a null pointer with n > 0.  n <= 0 launches nothing.
+ * sr_sun_shade: a per-pixel relighting of the composited albedo (it does not re-composite per sample).  With v = vis[i] (DEVICE fp32)
+ * and c = 0..2, in fp32 in this order with contraction off: q = 1 - v, k = q sky[i][c], irr = v + k, x = albedo[i][c] irr,
+ * rgb[i][c] = x clamped to [0, 1]; a NaN x stays NaN.  albedo / sky / rgb are DEVICE fp32 rows with strides >= 3 floats.
+ * Neither entry synchronises with the host: capturable. */
+int sr_sun_rays(const float* rays, int ray_stride, const float* depth, int64_t n, const double* center, double range, double max_alt,
+                const float* sun_d, double bias_abs, double bias_rel, float* out, int out_stride, uint8_t* valid, double* latlonalt,
+                void* stream);
+int sr_sun_shade(const float* albedo, int albedo_stride, const float* sky, int sky_stride, const float* vis, int64_t n, float* rgb,
+                 int rgb_stride, void* stream);
+
 /* ---- cloud fusion: eval_s2p.project_cloud_into_utm_grid (eval_s2p.py:175-226) ---------------------------------
  * sr_cloud_grid bins a UTM cloud (east / north / alt (N,) DEVICE fp64, sr_depth_to_utm's outputs) into a map_h x map_w grid and keeps
  * per cell the min (mode 0), max (1), mean (2) or median (3) of the altitudes that landed in it: out (map_h, map_w) DEVICE fp64, NaN

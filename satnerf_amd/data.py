@@ -203,6 +203,61 @@ def ortho_rays(grid, zone, min_alt, max_alt, center, scene_range, sun_d, device=
     return (rays, latlon) if return_latlon else rays
 
 
+def sun_rays(rays, depth, center, scene_range, max_alt, sun_d=None, bias=None, n_samples=None, out=None, return_valid=False,
+             return_latlonalt=False):
+    """The (N, 11) fp32 block of rays from rendered surface points towards the sun, on the GPU (csrc/sun_rays.hip, DESIGN.md section
+    7.14).  Row i starts at ``P = o + d * depth[i]`` of primary ray ``rays[i]`` and runs along the sun vector -- the call's ``sun_d``
+    (east, north, up; 3 values, not necessarily a unit vector) or, with ``sun_d=None``, the ray's own columns 8:11 -- turned into the
+    east / north / up frame of P's geodetic position, i.e. into the scene's normalised ECEF frame.  near = the bias, far = where the ray
+    reaches ``max_alt`` (metres) on the local tangent plane, at least near; columns 8:11 carry the sun vector as given.  Rendering these
+    rays and keeping ``transparency[:, -1]`` is what ``rendering.render_sun_visibility`` does.
+
+    ``center`` (3,) / ``scene_range``: the scene's ECEF normalisation.  ``bias`` keeps a ray from starting inside the surface it leaves:
+    ``None`` = one sample interval of the primary ray, (far - near) / ``n_samples`` (which is then required); a float = an absolute
+    distance in scene units.  The default is a derived quantity, not a tuned one: nobody has evaluated it on a trained scene.
+    far grows as 1 / sin(elevation) and is not capped, so the samples of a very low sun thin out accordingly.
+
+    A ray whose depth or surface point is not finite, or whose sun vector is zero, not finite or at or below the horizon, is invalid:
+    its row is the finite zero-length ray [o, d, 0, 0, sun].  ``out``: an (N, >=11) fp32 device tensor whose columns 0..10 are written.
+    Returns the rays, followed by ``valid`` (N,) bool with ``return_valid`` and ``latlonalt`` (3, N) fp64 (lat, lon degrees, alt metres
+    of the surface points; ``rendering.latlonalt_from_depth``'s bits) with ``return_latlonalt``."""
+    from . import ops
+
+    if not (torch.is_tensor(rays) and rays.is_cuda and torch.is_tensor(depth) and depth.is_cuda) or (
+            out is not None and not (torch.is_tensor(out) and out.is_cuda)):
+        raise ValueError("sun_rays runs on the GPU: satnerf_amd has no CPU path")
+    if rays.dim() != 2 or rays.shape[1] < 11:
+        raise ValueError(f"rays must be (N, 11) with the sun direction in columns 8:11, got {tuple(rays.shape)}")
+    if depth.numel() != rays.shape[0]:
+        raise ValueError(f"depth must hold one value per ray ({rays.shape[0]}), got {tuple(depth.shape)}")
+    if not float(scene_range) > 0:
+        raise ValueError(f"scene_range must be > 0, got {scene_range}")
+    if bias is None:
+        if n_samples is None or int(n_samples) < 1:
+            raise ValueError("bias=None means one sample interval of the primary ray: pass n_samples (>= 1), or an absolute bias")
+        bias_abs, bias_rel = 0.0, 1.0 / int(n_samples)
+    else:
+        bias_abs, bias_rel = float(bias), 0.0
+        if not (math.isfinite(bias_abs) and bias_abs >= 0):
+            raise ValueError(f"bias must be finite and >= 0, got {bias}")
+    sun = None
+    if sun_d is not None:
+        sun = [float(v) for v in (sun_d.tolist() if hasattr(sun_d, "tolist") else sun_d)]
+        if len(sun) != 3:
+            raise ValueError(f"sun_d must hold 3 values, got {len(sun)}")
+    ctr = [float(v) for v in (center.tolist() if hasattr(center, "tolist") else center)]
+    r32 = rays if rays.dtype == torch.float32 and rays.stride(1) == 1 else rays.float().contiguous()
+    with torch.cuda.device(rays.device):
+        sr, valid, lla = ops.sun_rays(r32, depth.reshape(-1).float().contiguous(), ctr, scene_range, max_alt, sun, bias_abs, bias_rel, out=out,
+                                      want_latlonalt=return_latlonalt)
+    res = (sr[:, :11],)  # a wider ``out`` keeps its other columns to itself
+    if return_valid:
+        res += (valid.bool(),)
+    if return_latlonalt:
+        res += (lla,)
+    return res if len(res) > 1 else res[0]
+
+
 def read_scene_loc(root_dir):
     """(center (3,) fp32 tensor, scene_range float) from ``root_dir/scene.loc`` as ``SatelliteDataset.__init__`` loads them
     (datasets/satellite.py:108-110): both rounded to fp32 (``scene_range`` is the fp32 maximum of the three scales, returned as a

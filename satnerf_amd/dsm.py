@@ -390,7 +390,8 @@ def _zone_of_center(center, device):
     return utm_zone(*torch.stack([lat[0], lon[0]]).cpu().tolist())
 
 
-def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, sun_d, roi=None, grid=None, zone=None, geometry_only=False):
+def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, sun_d, roi=None, grid=None, zone=None, geometry_only=False,
+                     shadows=None):
     """Render a nadir DSM of a trained field: ``data.ortho_rays`` over the grid -> ``render_image_outputs`` (once, no grad) ->
     :func:`ortho_dsm_from_depth`.  Every cell gets exactly one altitude, sampled along its own vertical, so the raster has no holes
     behind leaning buildings and involves no splat convention.
@@ -403,10 +404,18 @@ def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, su
     Returns (DSM, outputs).  ``outputs`` is the dict of ``render_image_outputs``; its per-ray tensors are in grid order, so
     ``outputs["rgb"].view(ysize, xsize, 3)`` is the true-ortho colour image, and likewise "albedo" (.., 3), "sun" (.., 1), "beta" (.., 1),
     "depth" / "acc" (ysize, xsize).  Cells outside the footprint the field was trained on are extrapolation: no footprint or visibility
-    mask is built.  ``geometry_only``: the render is ``rendering.render_depth`` and ``outputs`` holds "depth" and "acc" only."""
-    from .data import _ortho_grid, ortho_rays
-    from .rendering import render_depth, render_image_outputs
+    mask is built.  ``geometry_only``: the render is ``rendering.render_depth`` and ``outputs`` holds "depth" and "acc" only.
 
+    ``shadows="geometry"`` answers "which cells are in shadow at this sun position?": it adds ``outputs["sun_geo"]`` (ysize * xsize,), the
+    transparency of the learned density between each cell's rendered surface and the sun at ``sun_d``
+    (``rendering.render_sun_visibility`` on the rendered depths; NaN where the sun ray is invalid), and with the full render also
+    ``outputs["rgb_geo"]`` (.., 3) = ``ops.sun_shade`` of "albedo", "sky" and "sun_geo", a per-pixel relighting of the composited
+    albedo.  The DSM and every other output are those of ``shadows=None``."""
+    from .data import _ortho_grid, ortho_rays
+    from .rendering import render_depth, render_image_outputs, render_sun_visibility
+
+    if shadows not in (None, "geometry"):
+        raise ValueError(f"shadows must be None or 'geometry', got {shadows!r}")
     if (roi is None) == (grid is None):
         raise ValueError("exactly one of roi= and grid= sizes the DSM")
     grid = _ortho_grid(grid_from_roi(roi) if roi is not None else grid)
@@ -431,4 +440,9 @@ def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, su
                 outputs = {k: v for k, v in render_depth(models, rays, ts, args).items() if k in ("depth", "acc")}
             else:
                 outputs = render_image_outputs(models, rays, ts, args)
+            if shadows == "geometry":
+                outputs["sun_geo"] = render_sun_visibility(models, rays, ts, args, center, scene_range, max_alt, sun_d=sun_d,
+                                                           depth=outputs["depth"])["sun_geo"]
+                if not geometry_only:
+                    outputs["rgb_geo"] = ops.sun_shade(outputs["albedo"], outputs["sky"], outputs["sun_geo"])
         return ortho_dsm_from_depth(outputs["depth"], grid, max_alt, scene_range, zone=str(zone), roi=roi), outputs

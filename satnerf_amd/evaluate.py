@@ -10,9 +10,9 @@ import os
 import numpy as np
 import torch
 
-from . import metrics, visualize
+from . import metrics, ops, visualize
 from .dsm import dsm_from_depth, dsm_mae
-from .rendering import latlonalt_from_depth, render_image_outputs
+from .rendering import latlonalt_from_depth, render_image_outputs, render_sun_visibility
 
 
 def evaluate_image(models, rays, ts, rgbs, h, w, args, center=None, scene_range=None, roi=None, gt=None, gt_mask=None):
@@ -114,7 +114,24 @@ def sun_interp(models, rays, ts, args, h, w, upper, lower, center, scene_range, 
     fp64, per-angle output dicts and (h, w) fp32 altitude images, all in sweep order; ``order`` = the strips' layout as sweep
     positions (``order="reference"``: ``reference_strip_order``; ``"sweep"``: as rendered); ``strips`` = {"sun", "albedo", "rgb"} from
     ``visualize.sun_strip`` / ``rgb_strip`` (cropped, as the reference's summary) and, with ``lut``, "depth" = ``visualize.dsm_strip``
-    over the altitude images."""
+    over the altitude images.  Every shadow of this sweep comes from the ``sun_v`` head, a regression on the training images' sun
+    directions; ``sun_interp_shadows`` is the same sweep with the shadows cast through the density as well."""
+    return sun_interp_shadows(models, rays, ts, args, h, w, upper, lower, center, scene_range, n_interp=n_interp, lut=lut, order=order)
+
+
+def sun_interp_shadows(models, rays, ts, args, h, w, upper, lower, center, scene_range, n_interp=10, lut=None, order="reference", shadows="head",
+                       max_alt=None):
+    """``sun_interp`` with a choice of where the shadows come from.  ``shadows="head"`` (the default) is
+    ``sun_interp`` itself: arguments, draws and results.  ``shadows="geometry"`` (needs ``max_alt``, the scene's upper altitude bound in metres) adds to each
+    direction's output dict "sun_geo" (N, 1), the transparency of the learned density between the rendered surface and the sun
+    (``rendering.render_sun_visibility`` on that direction's depths), and "rgb_geo" (N, 3) = ``ops.sun_shade`` of the direction's
+    "albedo", "sky" and "sun_geo": a per-pixel relighting of the composited albedo, not a per-sample re-compositing.  The strips gain
+    "sun_geo" and "rgb_geo"; every other key is what ``shadows="head"`` returns.  (The keyword lives on this name, not on ``sun_interp``,
+    whose parameter list is pinned as the reference's.)"""
+    if shadows not in ("head", "geometry"):
+        raise ValueError(f"shadows must be 'head' or 'geometry', got {shadows!r}")
+    if shadows == "geometry" and max_alt is None:
+        raise ValueError("shadows='geometry' needs max_alt, the scene's upper altitude bound in metres")
     n = rays.shape[0]
     if int(h) * int(w) != n:
         raise ValueError(f"h * w = {int(h) * int(w)} does not match the {n} rays")
@@ -130,12 +147,19 @@ def sun_interp(models, rays, ts, args, h, w, upper, lower, center, scene_range, 
         for sun_d in dirs:
             swept[:, 8:11] = torch.from_numpy(sun_d.astype(np.float32)).to(swept.device)
             out = render_image_outputs(models, swept, ts, args)
+            if shadows == "geometry":
+                geo = render_sun_visibility(models, swept, ts, args, center, scene_range, max_alt, sun_d=sun_d, depth=out["depth"])["sun_geo"]
+                out["sun_geo"] = geo.view(n, 1)
+                out["rgb_geo"] = ops.sun_shade(out["albedo"], out["sky"], geo)
             outputs.append(out)
             alts.append(latlonalt_from_depth(swept, out["depth"], center, scene_range)[2].float().view(h, w))
         layout = reference_strip_order(angles) if order == "reference" else list(range(len(angles)))
         strips = {"sun": visualize.sun_strip([outputs[k]["sun"].view(h, w, 1) for k in layout]),
                   "albedo": visualize.rgb_strip([outputs[k]["albedo"].view(h, w, 3) for k in layout]),
                   "rgb": visualize.rgb_strip([outputs[k]["rgb"].view(h, w, 3) for k in layout])}
+        if shadows == "geometry":
+            strips["sun_geo"] = visualize.sun_strip([outputs[k]["sun_geo"].view(h, w, 1) for k in layout])
+            strips["rgb_geo"] = visualize.rgb_strip([outputs[k]["rgb_geo"].view(h, w, 3) for k in layout])
         if lut is not None:
             strips["depth"] = visualize.dsm_strip([alts[k] for k in layout], lut)
     return {"angles": angles, "sun_dirs": dirs, "outputs": outputs, "alts": alts, "order": layout, "strips": strips}

@@ -1062,6 +1062,54 @@ def ortho_rays(xoff, yoff, resolution, xsize, ysize, zone, min_alt, max_alt, cen
     return rays, latlon
 
 
+# ---- geometric sun visibility (csrc/sun_rays.hip) ------------------------------------------------------------------------------------
+def sun_rays(rays, depth, center, scene_range, max_alt, sun_d=None, bias_abs=0.0, bias_rel=0.0, out=None, want_latlonalt=False):
+    """sr_sun_rays: per primary ray (``rays`` (N, >=11), ``depth`` (N,)) the ray from its surface point towards the sun (``sun_d``: 3
+    floats for the whole call, or None for each ray's own columns 8:11), near = bias_abs + bias_rel * (far - near) of the primary ray.
+    Returns (sun_rays, valid, latlonalt): sun_rays = ``out`` (an (N, >=11) fp32 tensor with unit inner stride, columns 0..10 written)
+    or a new (N, 11) tensor; valid (N,) uint8; latlonalt (3, N) fp64 (lat, lon degrees, alt metres), or None."""
+    rays, stride = _rows(rays, "rays", 11)
+    n = rays.shape[0]
+    depth = _chk(depth, "depth")
+    if depth.dim() != 1 or depth.shape[0] != n:
+        raise ValueError(f"depth must be ({n},), one value per ray, got {tuple(depth.shape)}")
+    ctr = (C.c_double * 3)(*[float(v) for v in center])
+    sun = None if sun_d is None else (C.c_float * 3)(*[float(v) for v in sun_d])
+    if out is None:
+        sr, so = torch.empty(n, 11, dtype=torch.float32, device=rays.device), 11
+    else:
+        sr, so = _rows(out, "out", 11)
+        if sr.shape[0] != n:
+            raise ValueError(f"out must hold {n} rows, one per ray, got {tuple(sr.shape)}")
+        if n and sr.untyped_storage().data_ptr() == rays.untyped_storage().data_ptr():
+            raise ValueError("out must not share its storage with rays (the kernel reads one and writes the other)")
+    valid = torch.empty(n, dtype=torch.uint8, device=rays.device)
+    lla = torch.empty(3, n, dtype=torch.float64, device=rays.device) if want_latlonalt else None
+    _lib.call("sr_sun_rays", _p(rays), int(stride), _p(depth), n, C.addressof(ctr), float(scene_range), float(max_alt), sun, float(bias_abs),
+              float(bias_rel), _p(sr), int(so), _p(valid), _p(lla), _stream())
+    return sr, valid, lla
+
+
+def sun_shade(albedo, sky, vis, out=None):
+    """sr_sun_shade: rgb (N, 3) = clamp(albedo * (vis + (1 - vis) * sky), 0, 1) in fp32 per pixel, NaN where ``vis`` is NaN.  ``albedo``
+    / ``sky`` (N, >=3) rows (e.g. the columns of ``render_image_outputs``), ``vis`` (N,) or (N, 1); ``out``: an (N, >=3) fp32 tensor whose
+    columns 0..2 are written."""
+    albedo, sa = _rows(albedo, "albedo", 3)
+    sky, ss = _rows(sky, "sky", 3)
+    n = albedo.shape[0]
+    if sky.shape[0] != n or vis.numel() != n or vis.dim() > 2:
+        raise ValueError(f"albedo, sky and vis must hold one row per pixel, got {tuple(albedo.shape)}, {tuple(sky.shape)}, {tuple(vis.shape)}")
+    vis = _chk(vis.reshape(-1), "vis")
+    if out is None:
+        rgb, so = torch.empty(n, 3, dtype=torch.float32, device=albedo.device), 3
+    else:
+        rgb, so = _rows(out, "out", 3)
+        if rgb.shape[0] != n:
+            raise ValueError(f"out must hold {n} rows, one per pixel, got {tuple(rgb.shape)}")
+    _lib.call("sr_sun_shade", _p(albedo), int(sa), _p(sky), int(ss), _p(vis), n, _p(rgb), int(so), _stream())
+    return rgb[:, :3]
+
+
 # ---- cloud fusion (csrc/cloud_grid.hip) --------------------------------------------------------------------------------------------
 CLOUD_RULES = {"nearest": 0, "floor": 1}
 CLOUD_MODES = {"min": 0, "max": 1, "avg": 2, "med": 3}

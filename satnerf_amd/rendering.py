@@ -458,6 +458,25 @@ def render_depth(models, rays, ts, args, return_weights=False):
     Random draws per chunk are ``render_rays``' in order and shape -- the noise of the passes skipped here (solar correction) included --
     so a seed (or ``replay_rng``) gives the depths of the full render: bit for bit, as sigma's arithmetic and the compositing reduction
     are the full kernel's."""
+    n_total, dev = rays.shape[0], rays.device
+    chunks = _depth_chunks(models, rays, ts, args, return_weights)
+    typ, s_out = next(chunks)
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"typ": typ, "depth": e(n_total), "acc": e(n_total)}
+    if return_weights:
+        out.update(weights=e(n_total, s_out), transparency=e(n_total, s_out), z=e(n_total, s_out))
+    for i, n, o in chunks:
+        out["depth"][i:i + n] = o["depth"]
+        torch.sum(o["weights"], -1, out=out["acc"][i:i + n])
+        if return_weights:
+            out["weights"][i:i + n], out["transparency"][i:i + n], out["z"][i:i + n] = o["weights"], o["transparency"], o["z"]
+    return out
+
+
+def _depth_chunks(models, rays, ts, args, want_z):
+    """The chunk loop of ``render_depth`` as a generator: the arguments are checked, (typ, samples per ray of the finest pass) is
+    yielded first, then per ``args.chunk`` rows (first row, rows, {"depth", "weights", "transparency" and, with ``want_z``, "z"}) of
+    the finest pass.  ``render_sun_visibility`` walks it too and keeps one column per chunk."""
     if args.model not in ("sat-nerf", "s-nerf", "nerf"):
         raise ValueError(f"model {args.model} is not valid")
     if not rays.is_cuda:
@@ -473,10 +492,7 @@ def render_depth(models, rays, ts, args, return_weights=False):
     typ = "fine" if n_imp > 0 else "coarse"
     mode = _mode_of(args)
     s_out = s + n_imp
-    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-    out = {"typ": typ, "depth": e(n_total), "acc": e(n_total)}
-    if return_weights:
-        out.update(weights=e(n_total, s_out), transparency=e(n_total, s_out), z=e(n_total, s_out))
+    yield typ, s_out
 
     def geometry_ok(model, k):
         return (_FUSED_RENDER and mode in ("bf16", "f16") and hasattr(model, "fused_forward") and hasattr(model, "t_embedding_dims") and model.fused_forward(mode)
@@ -509,24 +525,105 @@ def render_depth(models, rays, ts, args, return_weights=False):
         r = rays[i:i + args.chunk].contiguous().float()
         n = r.shape[0]
         if not fused:
-            with _recorded_rands(return_weights) as rands:
+            with _recorded_rands(want_z) as rands:
                 res = render_rays(models, args, r, None if ts is None else ts[i:i + args.chunk], _ts_validated=True)
             o = {"depth": res[f"depth_{typ}"], "weights": res[f"weights_{typ}"], "transparency": res[f"transparency_{typ}"]}
-            if return_weights:  # render_rays does not return its depths: they are rebuilt from its uniform draws (rendering.py:62-78,118-121)
+            if want_z:  # render_rays does not return its depths: they are rebuilt from its uniform draws (rendering.py:62-78,118-121)
                 o["z"] = ops.ray_sample(r, rands[0], s)
                 if n_imp > 0:
                     o["z"] = ops.sample_pdf_merge(o["z"], res["weights_coarse"], rands[1])
         else:
             t = ts[i:i + args.chunk].contiguous().long().view(-1)
-            o = one_pass(models["coarse"], r, t, None, None if kernel else _rng.rand(n, s, dev), s, n_imp > 0 or return_weights)
+            o = one_pass(models["coarse"], r, t, None, None if kernel else _rng.rand(n, s, dev), s, n_imp > 0 or want_z)
             if n_imp > 0:
                 z_fine = ops.sample_pdf_merge(o["z"], o["weights"], _rng.rand(n, n_imp, dev))
                 o = one_pass(models["fine"], r, t, z_fine, None, s_out, True)
-        out["depth"][i:i + n] = o["depth"]
-        torch.sum(o["weights"], -1, out=out["acc"][i:i + n])
-        if return_weights:
-            out["weights"][i:i + n], out["transparency"][i:i + n], out["z"][i:i + n] = o["weights"], o["transparency"], o["z"]
-    return out
+        yield i, n, o
+
+
+class _MidpointRng:
+    """The draws of a render without perturbation: 0.5 for the stratified jitter (the stratum midpoints), (i + 0.5) / n_importance for
+    the importance draws, zeros for every normal draw.  ``render_rays`` and ``render_depth`` draw uniforms in the order stratified
+    [, importance] per chunk, which is how the two are told apart.  Nothing is taken from torch's generator; the constant tensors are
+    kept per shape and only ever read."""
+
+    def __init__(self, n_importance):
+        self.n_importance, self.rands, self.cache = int(n_importance), 0, {}
+
+    def _const(self, key, n, m, device, make):
+        key = (key, n, m, str(device))
+        if key not in self.cache:
+            self.cache[key] = make().to(device=device, dtype=torch.float32).expand(n, m).contiguous()
+        return self.cache[key]
+
+    def rand(self, n, m, device):
+        importance = self.n_importance > 0 and self.rands % 2 == 1
+        self.rands += 1
+        if importance:
+            return self._const("i", n, m, device, lambda: (torch.arange(m, dtype=torch.float64) + 0.5) / m)
+        return self._const("u", n, m, device, lambda: torch.full((1,), 0.5))
+
+    def randn(self, n, m, device):
+        return self._const("n", n, m, device, lambda: torch.zeros(1))
+
+
+@contextlib.contextmanager
+def _midpoint_rng(enabled, n_importance):
+    global _rng
+    if not enabled:
+        yield None
+        return
+    prev, _rng = _rng, _MidpointRng(n_importance)
+    try:
+        yield _rng
+    finally:
+        _rng = prev
+
+
+@torch.no_grad()
+def render_sun_visibility(models, rays, ts, args, center, scene_range, max_alt, sun_d=None, depth=None, bias=None, perturb=False):
+    """Geometric sun visibility of a whole image: per primary ray, the transparency the learned density leaves
+    between the rendered surface point and the sun -- the quantity the solar correction (metrics.py:27-33) trains the ``sun_v`` head
+    towards, computed instead of regressed, so it holds for sun positions outside the training images'.
+
+    rays (N, >=11) -> ``{"typ", "depth" (N,), "sun_geo" (N,), "valid" (N,) bool}``.  ``depth``: the primary rays' depths (e.g.
+    ``render_image_outputs(...)["depth"]``; then only the sun pass is paid for), or None to render them with ``render_depth``.
+    ``data.sun_rays`` builds the sun rays from them (``center`` / ``scene_range`` / ``max_alt`` the scene's ECEF normalisation and upper
+    altitude bound; ``sun_d`` one (east, north, up) vector for the call or None for each ray's columns 8:11; ``bias`` as there, default
+    one interval of the primary ray's ``args.n_samples``), and the depth-only render walks them chunk by chunk (``args.chunk``), keeping
+    of each chunk only ``transparency[:, -1]``: the transmittance in front of the last sample under the reference's compositing
+    (models/satnerf.py:52-63).  It is not ``1 - acc``: the last sample's delta is 1e10 and the density a softplus, so ``acc`` is 1 on
+    every ray.  The sun pass is ``render_depth``'s on every route (the one-launch trunk-and-density kernel where ``ops.render_fused_ok``
+    holds, ``render_rays`` elsewhere; the fine pass with ``n_importance > 0``); no (N, S) tensor of the whole image is allocated.
+
+    ``perturb=False``: samples sit at the stratum midpoints, importance draws at (i + 0.5) / n_importance, the density noise is off,
+    no random number is drawn (the caller's generator is untouched) and two calls return the same bits; this covers the primary render
+    of ``depth=None`` too.  ``perturb=True`` draws as ``render_depth`` does.  Invalid sun rays (``data.sun_rays``) reach the kernels as
+    finite zero-length rays and come back as NaN with ``valid`` False.  ``sat-nerf`` and ``s-nerf`` only: the classic ``nerf`` has no
+    sun and no ECEF frame."""
+    from .data import sun_rays
+
+    if args.model == "nerf":
+        raise ValueError("render_sun_visibility: the classic nerf has no sun direction and no ECEF frame (sat-nerf and s-nerf only)")
+    if args.model not in ("sat-nerf", "s-nerf"):
+        raise ValueError(f"model {args.model} is not valid")
+    if not rays.is_cuda:
+        raise RuntimeError("rays must be on the GPU: satnerf_amd has no CPU path")
+    n_total = rays.shape[0]
+    with _midpoint_rng(not perturb, args.n_importance):
+        if depth is None:
+            depth = render_depth(models, rays, ts, args)["depth"]
+        elif not (torch.is_tensor(depth) and depth.is_cuda and depth.numel() == n_total):
+            raise ValueError(f"depth must hold one value per ray ({n_total}) on the GPU")
+        depth = depth.reshape(-1).float().contiguous()
+        srays, valid = sun_rays(rays, depth, center, scene_range, max_alt, sun_d=sun_d, bias=bias, n_samples=args.n_samples, return_valid=True)
+        sun_geo = torch.empty(n_total, dtype=torch.float32, device=rays.device)
+        chunks = _depth_chunks(models, srays, ts, args, False)
+        typ, _ = next(chunks)
+        for i, n, o in chunks:
+            sun_geo[i:i + n] = o["transparency"][:, -1]
+    sun_geo.masked_fill_(~valid, float("nan"))
+    return {"typ": typ, "depth": depth, "sun_geo": sun_geo, "valid": valid}
 
 
 def latlonalt_from_depth(rays, depth, center, scene_range):
