@@ -607,6 +607,49 @@ int sr_sun_rays(const float* rays, int ray_stride, const float* depth, int64_t n
 int sr_sun_shade(const float* albedo, int albedo_stride, const float* sky, int sky_stride, const float* vis, int64_t n, float* rgb,
                  int rgb_stride, void* stream);
 
+/* ---- ray casting against a DSM raster: the raster as geometry -----------------------------------------------------
+ * hgt (ysize, xsize) DEVICE fp32 is a DSM raster in sr_dsm_rasterize's layout, a value that is not finite = no surface.  Grid frame, fp64
+ * metres: a point (E, N, alt) has x = E - xoff, y = yoff - N, z = alt; cell (j, c) is x in [c r, (c+1) r), y in [j r, (j+1) r); a
+ * finite cell is the solid column z <= h over that square, any other cell is empty and passed through.
+ * The walk, one lane per ray, all fp64 with contraction off.  A ray is the straight segment A -> B, s in [0, 1], clipped to the grid's
+ * rectangle first (a segment that misses it is a miss).  Cells are visited in order of s.  The parameter of the crossing of the
+ * line x = k r is (k r - xA) / (xB - xA), computed from the absolute index k, never accumulated; rows likewise.  The cell the segment
+ * is in at a parameter s is defined by these values alone (for xB > xA the largest c whose line is crossed at or before s, the
+ * smallest for xB < xA, and the c with c r <= xA < (c+1) r for xB = xA): where a position is floored, at the entry, the index is
+ * corrected against them, so a result does not depend on how the walk got there.  On a tie (both crossings at the same s) both
+ * indices step: the two cells touched at a point are not visited.  Hit rule for a visited finite cell entered at s_in and left at
+ * s_out = min(its next crossing, 1), with z(s) = zA + s (zB - zA): z(s_in) <= h hits at s_in (a wall, or a start inside the column);
+ * otherwise z(s_out) <= h hits at (h - zA) / (zB - zA) (the top); otherwise the walk goes on.  The first hit ends it; reaching s = 1
+ * or leaving the grid is a miss.  Crossing values of neighbouring lines must differ (r far above the spacing of the coordinates).
+ * sr_heightfield_blockmax: blockmax (ceil(ysize / 16), ceil(xsize / 16)) DEVICE fp32 = the maximum of the finite cells of each 16 x 16
+ * block, -inf where there is none; gmax (1 DEVICE fp32) = the maximum of the raster, -inf likewise.  Two launches, no atomics.
+ * sr_heightfield_cast: n rays, given either in the scene frame -- rays (DEVICE fp32 rows, ray_stride >= 8: o(3) d(3) near far), center
+ * (3 HOST doubles), range, zone (1..60), xoff, yoff; A and B are the UTM images of o + d near and o + d far by exactly
+ * sr_depth_to_utm's arithmetic, the path between them is taken as the chord (sag <= run^2 / (8 R)), and t = near + s (far - near) --
+ * or as grid-frame segments seg_a, seg_b ((n, 3) DEVICE fp64; then rays is NULL, center .. yoff are ignored and t = s).  Outputs:
+ * depth (n,) fp32 = t evaluated in fp64 and rounded once, NaN on a miss; cell (n,) int32 = j xsize + c, -1 on a miss; s (n,) fp64,
+ * NaN on a miss, may be NULL; seg (n, 6) DEVICE fp64 = (E, N, alt) of A and of B as sr_depth_to_utm gives them: required in the ray
+ * form, where a first launch writes it and the walk reads it (the segment that was walked), and NULL with segments.
+ * A ray with an endpoint that is not finite, or with far < near, is a miss, never a fault.
+ * sr_heightfield_shadow: out (ysize, xsize) DEVICE fp32 = 1 lit, 0 shadowed, NaN where the cell is empty, the grid frame taken as flat.
+ * For every finite cell A = (cell centre, h + bias), bias >= 0 metres; the direction is the unit vector of sun_d (3 HOST doubles:
+ * east, north, up, up > 0), i.e. (uE, -uN, uU) in the grid frame; B is where the ray reaches gmax, above which nothing can block; a
+ * start at or above gmax is lit.  The walk is sr_heightfield_cast's, with the start cell passed through whatever its height: the ray
+ * leaves the surface it stands on (a rule, not a tuned bias).
+ * accelerate = 1 (cast and shadow) takes the two-level walk: block by block, descending into a block's cells only where the segment's
+ * lowest altitude over the block is <= the block's maximum, and ending a rising ray once it is above gmax; it then needs blockmax
+ * and gmax of sr_heightfield_blockmax (the shadow needs gmax always).  Its results are bit-identical to accelerate = 0.
+ * Errors (nothing is launched): xsize or ysize < 1, xsize * ysize >= 2^31, resolution not finite or <= 0, a null pointer, accelerate
+ * outside {0, 1}, both or neither of rays and seg_a / seg_b, seg with segments, ray_stride < 8, zone outside 1..60, range not finite
+ * or <= 0, xoff / yoff / center not finite, a bias negative or not finite, a sun_d that is not finite, zero or has up <= 0.  n <= 0
+ * launches nothing.  No entry synchronises with the host: capturable. */
+int sr_heightfield_blockmax(const float* hgt, int xsize, int ysize, float* blockmax, float* gmax, void* stream);
+int sr_heightfield_cast(const float* hgt, int xsize, int ysize, double resolution, const float* blockmax, const float* gmax, int accelerate,
+                        const float* rays, int ray_stride, const double* center, double range, int zone, double xoff, double yoff,
+                        const double* seg_a, const double* seg_b, int64_t n, float* depth, int* cell, double* s, double* seg, void* stream);
+int sr_heightfield_shadow(const float* hgt, int xsize, int ysize, double resolution, const float* blockmax, const float* gmax,
+                          int accelerate, const double* sun_d, double bias, float* out, void* stream);
+
 /* ---- cloud fusion: eval_s2p.project_cloud_into_utm_grid (eval_s2p.py:175-226) ---------------------------------
  * sr_cloud_grid bins a UTM cloud (east / north / alt (N,) DEVICE fp64, sr_depth_to_utm's outputs) into a map_h x map_w grid and keeps
  * per cell the min (mode 0), max (1), mean (2) or median (3) of the altitudes that landed in it: out (map_h, map_w) DEVICE fp64, NaN

@@ -446,3 +446,75 @@ def render_ortho_dsm(models, ts, args, center, scene_range, min_alt, max_alt, su
                 if not geometry_only:
                     outputs["rgb_geo"] = ops.sun_shade(outputs["albedo"], outputs["sky"], outputs["sun_geo"])
         return ortho_dsm_from_depth(outputs["depth"], grid, max_alt, scene_range, zone=str(zone), roi=roi), outputs
+
+
+# ---- a DSM as geometry ---------------------------------------------------------------------------------------
+def _surface(dsm, name="dsm"):
+    """The (ysize, xsize) fp32 device raster of a :class:`DSM`, contiguous."""
+    if not isinstance(dsm, DSM):
+        raise ValueError(f"{name} must be a DSM (raster, xoff, yoff, resolution, zone), got {type(dsm).__name__}")
+    t = dsm.dsm
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError(f"{name}.dsm must be a GPU tensor: satnerf_amd has no CPU path")
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"{name}.dsm must be a non-empty (ysize, xsize) raster, got shape {tuple(t.shape)}")
+    if not float(dsm.resolution) > 0:
+        raise ValueError(f"{name}.resolution must be > 0, got {dsm.resolution}")
+    return t.float().contiguous()
+
+
+def cast_rays(dsm, rays, center, scene_range, zone=None, accelerate=True):
+    """Where each ray meets a DSM taken as geometry (csrc/heightfield.hip): every finite cell of ``dsm`` (a :class:`DSM`) is a solid
+    column, a NaN cell is empty, and a ray is the straight chord between the UTM images of its near and far points, walked through the
+    raster's cells until it enters a column.  ``rays`` (N, >=8) fp32 on the GPU in the scene frame of ``center`` / ``scene_range``;
+    ``zone`` (1..60 or "17R") defaults to the DSM's.  Returns ``{"depth": (N,) fp32 in the rays' own units, NaN on a miss, "cell": (N,)
+    int32 = j * xsize + c of the column that was hit, -1 on a miss, "hit": (N,) bool}``: the depth a DSM implies in a view's pixels,
+    occlusion included, and the cell each pixel sees.  A ray with a non-finite end or far < near is a miss.  ``accelerate=False`` takes
+    the plain walk instead of the two-level one; the results are the same bits."""
+    hgt = _surface(dsm)
+    if not (torch.is_tensor(rays) and rays.is_cuda):
+        raise ValueError("rays must be a GPU tensor: satnerf_amd has no CPU path")
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise ValueError(f"rays must be (N, >=8): origin, direction, near, far, got {tuple(rays.shape)}")
+    if not float(scene_range) > 0:
+        raise ValueError(f"scene_range must be > 0, got {scene_range}")
+    if zone is None and not dsm.zone:
+        raise ValueError("the DSM carries no UTM zone: pass zone= explicitly")
+    number = _zone_number(dsm.zone if zone is None else zone)
+    ctr = [float(v) for v in (center.tolist() if hasattr(center, "tolist") else center)]
+    r32 = rays if rays.dtype == torch.float32 and rays.stride(1) == 1 else rays.float().contiguous()
+    with torch.cuda.device(hgt.device):
+        depth, cell, _, _ = ops.heightfield_cast(hgt, dsm.resolution, rays=r32, center=ctr, scene_range=scene_range, zone=number,
+                                                 xoff=dsm.xoff, yoff=dsm.yoff, accelerate=accelerate)
+    return {"depth": depth, "cell": cell, "hit": cell >= 0}
+
+
+def shadow_mask(dsm, sun_d, bias=0.0, accelerate=True):
+    """The shadows a DSM casts on itself under one sun direction: an (ysize, xsize) fp32 device raster, 1.0 lit, 0.0 shadowed, NaN where
+    the cell is NaN.  From every finite cell a ray leaves the cell centre at its height + ``bias`` (metres, >= 0) along ``sun_d`` (3
+    values: east, north, up, as ``data.sun_direction`` returns them; not necessarily a unit vector) and is walked through the raster up
+    to its highest cell; the cell it starts in never shades itself.  The grid is taken as flat.  Raises ValueError for a sun at or below
+    the horizon."""
+    hgt = _surface(dsm)
+    sun = [float(v) for v in (sun_d.tolist() if hasattr(sun_d, "tolist") else sun_d)]
+    if len(sun) != 3 or not all(math.isfinite(v) for v in sun):
+        raise ValueError(f"sun_d must hold 3 finite values (east, north, up), got {sun}")
+    if not sun[2] > 0:
+        raise ValueError(f"the sun is at or below the horizon (up = {sun[2]}): there is no shadow mask to cast")
+    if not (math.isfinite(float(bias)) and float(bias) >= 0):
+        raise ValueError(f"bias must be finite and >= 0 metres, got {bias}")
+    with torch.cuda.device(hgt.device):
+        return ops.heightfield_shadow(hgt, dsm.resolution, sun, bias=float(bias), accelerate=accelerate)
+
+
+def sun_visibility_from_dsm(dsm, rays, depth, center, scene_range, max_alt, sun_d=None, bias=None, n_samples=None):
+    """The DSM's shadows in a view's own pixels, shaped like ``rendering.render_sun_visibility``'s "sun_geo": ``data.sun_rays`` from the
+    rendered surface points (``rays`` (N, >=11), ``depth`` (N,); ``sun_d``, ``bias`` and ``n_samples`` as there) followed by
+    :func:`cast_rays`.  Returns (N,) fp32: 1 where the sun ray misses the DSM, 0 where it meets it, NaN for the rows ``sun_rays`` calls
+    invalid.  The sun rays end at ``max_alt``: a DSM column above it cannot shade."""
+    from .data import sun_rays
+
+    sr, valid = sun_rays(rays, depth, center, scene_range, max_alt, sun_d=sun_d, bias=bias, n_samples=n_samples, return_valid=True)
+    hit = cast_rays(dsm, sr, center, scene_range)["hit"]
+    lit = torch.where(hit, 0.0, 1.0).to(torch.float32)
+    return torch.where(valid, lit, torch.full_like(lit, float("nan")))

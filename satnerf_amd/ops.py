@@ -1110,8 +1110,87 @@ def sun_shade(albedo, sky, vis, out=None):
     return rgb[:, :3]
 
 
+# ---- ray casting against a DSM raster (csrc/heightfield.hip) -------------------------------------------------------------------------
+def _heightfield(hgt):
+    hgt = _chk(hgt, "hgt")
+    if hgt.dim() != 2 or hgt.numel() == 0:
+        raise ValueError(f"hgt must be a non-empty (ysize, xsize) raster, got {tuple(hgt.shape)}")
+    return hgt, int(hgt.shape[1]), int(hgt.shape[0])
+
+
+def heightfield_blockmax(hgt):
+    """sr_heightfield_blockmax: (blockmax (ceil(ysize / 16), ceil(xsize / 16)) fp32, gmax (1,) fp32) of an (ysize, xsize) fp32 device
+    raster: the maxima of the finite cells of its 16 x 16 blocks and of the whole raster, -inf where there is no finite cell."""
+    hgt, xsize, ysize = _heightfield(hgt)
+    blockmax = torch.empty(-(-ysize // 16), -(-xsize // 16), dtype=torch.float32, device=hgt.device)
+    gmax = torch.empty(1, dtype=torch.float32, device=hgt.device)
+    _lib.call("sr_heightfield_blockmax", _p(hgt), xsize, ysize, _p(blockmax), _p(gmax), _stream())
+    return blockmax, gmax
+
+
+def _heightfield_maxima(hgt, accelerate, maxima, always=False):
+    if maxima is None:
+        return heightfield_blockmax(hgt) if accelerate or always else (None, None)
+    blockmax, gmax = maxima
+    blockmax, gmax = _chk(blockmax, "blockmax"), _chk(gmax, "gmax")
+    if tuple(blockmax.shape) != (-(-hgt.shape[0] // 16), -(-hgt.shape[1] // 16)) or gmax.numel() != 1:
+        raise ValueError(f"maxima must be heightfield_blockmax's pair for a {tuple(hgt.shape)} raster, got {tuple(blockmax.shape)} and "
+                         f"{tuple(gmax.shape)}")
+    return blockmax, gmax
+
+
+def heightfield_cast(hgt, resolution, rays=None, center=None, scene_range=None, zone=None, xoff=None, yoff=None, seg_a=None, seg_b=None,
+                     accelerate=True, maxima=None, want_s=False, want_seg=False):
+    """sr_heightfield_cast: the first column of the (ysize, xsize) fp32 device raster ``hgt`` that each ray enters.  The rays are either
+    ``rays`` (N, >=8) fp32 in the scene frame (with ``center``, ``scene_range``, ``zone`` 1..60 and the raster's ``xoff`` / ``yoff``) or
+    the grid-frame segments ``seg_a`` / ``seg_b`` (N, 3) fp64.  ``maxima``: heightfield_blockmax's pair when it is at hand (computed here
+    otherwise, for ``accelerate``).  Returns (depth (N,) fp32, NaN on a miss; cell (N,) int32, -1 on a miss; s (N,) fp64 or None; seg
+    (N, 6) fp64 = the UTM (E, N, alt) of both ends of the walked segment, or None)."""
+    hgt, xsize, ysize = _heightfield(hgt)
+    if (rays is None) == (seg_a is None and seg_b is None):
+        raise ValueError("give either rays (scene frame) or seg_a and seg_b (grid frame)")
+    ctr = None
+    if rays is not None:
+        rays, stride = _rows(rays, "rays", 8)
+        n = rays.shape[0]
+        if center is None or scene_range is None or zone is None or xoff is None or yoff is None:
+            raise ValueError("rays in the scene frame need center, scene_range, zone, xoff and yoff")
+        ctr = (C.c_double * 3)(*[float(v) for v in center])
+        frame = (C.addressof(ctr), float(scene_range), int(zone), float(xoff), float(yoff))
+    else:
+        seg_a, seg_b = _chk(seg_a, "seg_a", torch.float64), _chk(seg_b, "seg_b", torch.float64)
+        if seg_a.dim() != 2 or seg_a.shape[1] != 3 or seg_a.shape != seg_b.shape:
+            raise ValueError(f"seg_a / seg_b must be two (N, 3) tensors, got {tuple(seg_a.shape)} / {tuple(seg_b.shape)}")
+        if want_seg:
+            raise ValueError("want_seg belongs to rays in the scene frame: segments are walked as given")
+        n, stride, frame = seg_a.shape[0], 0, (None, 1.0, 0, 0.0, 0.0)
+    blockmax, gmax = _heightfield_maxima(hgt, accelerate, maxima)
+    dev = hgt.device
+    depth = torch.empty(n, dtype=torch.float32, device=dev)
+    cell = torch.empty(n, dtype=torch.int32, device=dev)
+    s = torch.empty(n, dtype=torch.float64, device=dev) if want_s else None
+    seg = torch.empty(n, 6, dtype=torch.float64, device=dev) if rays is not None else None  # the entry's scratch in the ray form
+    if n == 0:  # an empty tensor has no address to tell the two forms apart by
+        return depth, cell, s, seg if want_seg else None
+    _lib.call("sr_heightfield_cast", _p(hgt), xsize, ysize, float(resolution), _p(blockmax), _p(gmax), int(bool(accelerate)), _p(rays),
+              int(stride), *frame, _p(seg_a), _p(seg_b), n, _p(depth), _p(cell), _p(s), _p(seg), _stream())
+    return depth, cell, s, seg if want_seg else None
+
+
+def heightfield_shadow(hgt, resolution, sun_d, bias=0.0, accelerate=True, maxima=None):
+    """sr_heightfield_shadow: the (ysize, xsize) fp32 mask of the raster ``hgt`` under the sun direction ``sun_d`` (3 floats: east, north,
+    up; up > 0): 1 lit, 0 shadowed, NaN where the cell holds no surface.  ``bias`` >= 0 metres lifts the start of every ray."""
+    hgt, xsize, ysize = _heightfield(hgt)
+    sun = (C.c_double * 3)(*[float(v) for v in sun_d])
+    blockmax, gmax = _heightfield_maxima(hgt, accelerate, maxima, always=True)
+    out = torch.empty_like(hgt)
+    _lib.call("sr_heightfield_shadow", _p(hgt), xsize, ysize, float(resolution), _p(blockmax), _p(gmax), int(bool(accelerate)),
+              C.addressof(sun), float(bias), _p(out), _stream())
+    return out
+
+
 # ---- cloud fusion (csrc/cloud_grid.hip) --------------------------------------------------------------------------------------------
-CLOUD_RULES = {"nearest": 0, "floor": 1}
+CLOUD_RULES ={"nearest": 0, "floor": 1}
 CLOUD_MODES = {"min": 0, "max": 1, "avg": 2, "med": 3}
 
 
