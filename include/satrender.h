@@ -650,6 +650,43 @@ int sr_heightfield_cast(const float* hgt, int xsize, int ysize, double resolutio
 int sr_heightfield_shadow(const float* hgt, int xsize, int ysize, double resolution, const float* blockmax, const float* gmax,
                           int accelerate, const double* sun_d, double bias, float* out, void* stream);
 
+/* ---- orthorectification onto a DSM raster: a view's pixels brought to the DSM's cells ----------------------------
+ * hgt, xsize, ysize, resolution, blockmax, gmax, accelerate: the raster of section 7.15 and sr_heightfield_blockmax's maxima (gmax is
+ * always needed, blockmax with accelerate = 1); xoff, yoff, zone (1..60): its place in UTM, cell (j, c) centred at E = xoff + (c + 0.5) r,
+ * N = yoff - (j + 0.5) r.  rpc = the 90 HOST doubles of sr_rpc_rays.  image = DEVICE pixels, fmt 0 uint8 (value v / 255) or 1 fp32
+ * (value v), pixel (row, col) channel ch at element row row_stride + col pix_stride + ch, channels 1..4, pix_stride >= channels,
+ * row_stride >= (width - 1) pix_stride + channels.  Pixel centres sit at integer (col, row), as sr_rpc_rays places them.
+ * Per cell i = j xsize + c, fp64 with contraction off:
+ *   h not finite: status 0 (empty), colour NaN, colrow NaN.
+ *   (col, row) = the RPC projection of (sr_utm_to_latlon's (lat, lon) of the cell centre, altitude h): colrow[i] = (col, row), always.
+ *   (col, row) not finite or outside [0, width - 1] x [0, height - 1]: status 3 (outside), colour NaN.
+ *   line of sight: A = (cell centre, h + bias), bias >= 0 metres.  h + bias >= gmax: visible.  Else B = the UTM image of the camera's
+ *   localisation of (col, row) at altitude gmax (sr_rpc_rays' Newton iteration), at altitude gmax, and A -> B is walked in the grid
+ *   frame by sr_heightfield_cast's walk with cell i itself passed through (the chord, the grid taken as flat): a hit gives status 2
+ *   (occluded), colour NaN; a miss status 1 (visible).  accelerate = 1 takes the two-level walk: the same bits.
+ *   a visible cell's colour[i][ch], mode 0 nearest: pixel (floor(row + 0.5), floor(col + 0.5)); mode 1 bilinear: with x0 = floor(col),
+ *   fx = col - x0 (rows likewise) ((1 - fx) p00 + fx p01) (1 - fy) + ((1 - fx) p10 + fx p11) fy; mode 2 bicubic: Keys' kernel with
+ *   a = -0.5 over the 4 x 4 taps x0 - 1 .. x0 + 2, weights w(1 + fx), w(fx), w(1 - fx), w(2 - fx), each row's columns summed first in
+ *   increasing index order, then the rows likewise.  Neighbour indices are clamped to the image (edge replicate).  Weights and sums
+ *   in fp64, rounded to fp32 once.  A NaN pixel under a tap propagates.
+ * Outputs: color (ysize, xsize, channels) DEVICE fp32, status (ysize, xsize) DEVICE uint8, colrow (ysize, xsize, 2) DEVICE fp64.
+ * Fusion: sum ((ysize, xsize, channels) DEVICE fp64) and count ((ysize, xsize) DEVICE int32), both or neither: a visible cell adds
+ * its fp32 colour to sum and 1 to count.  One lane owns one cell and calls follow one another on the stream: no atomics, the
+ * accumulation of several views is bitwise repeatable and in call order.  The caller zeroes them and divides.
+ * Two launches: the projection writes colrow and, into scratch, the status it decides and B; the second walks, samples and
+ * accumulates.  scratch: caller-owned DEVICE bytes (8-byte aligned), at least sr_orthorectify_scratch(xsize, ysize) (HOST only).
+ * stages 0 runs both, 1 the projection alone, 2 the second launch alone on the colrow and scratch a stages = 1 call with the same
+ * raster, camera and bias left (another image, mode or walk without projecting again; timing).
+ * Errors (nothing is launched): xsize or ysize < 1, xsize * ysize >= 2^31, resolution not finite or <= 0, xoff / yoff not finite, zone
+ * outside 1..60, accelerate outside {0, 1}, a null pointer, width or height < 1, channels outside 1..4, fmt outside {0, 1}, strides
+ * that overlap, mode outside 0..2, a bias negative or not finite, stages outside 0..2, one accumulator without the other, a zero RPC
+ * scale, scratch too small or misaligned.  Neither entry synchronises with the host: capturable. */
+int sr_orthorectify_scratch(int xsize, int ysize, int64_t* bytes);
+int sr_orthorectify(const float* hgt, int xsize, int ysize, double resolution, double xoff, double yoff, int zone, const float* blockmax,
+                    const float* gmax, int accelerate, const double* rpc, const void* image, int fmt, int width, int height, int channels,
+                    int64_t row_stride, int64_t pix_stride, int mode, double bias, int stages, void* scratch, int64_t scratch_bytes,
+                    float* color, uint8_t* status, double* colrow, double* sum, int* count, void* stream);
+
 /* ---- cloud fusion: eval_s2p.project_cloud_into_utm_grid (eval_s2p.py:175-226) ---------------------------------
  * sr_cloud_grid bins a UTM cloud (east / north / alt (N,) DEVICE fp64, sr_depth_to_utm's outputs) into a map_h x map_w grid and keeps
  * per cell the min (mode 0), max (1), mean (2) or median (3) of the altitudes that landed in it: out (map_h, map_w) DEVICE fp64, NaN

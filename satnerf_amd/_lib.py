@@ -141,6 +141,9 @@ SIGNATURES = {
     "sr_heightfield_blockmax": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "sr_heightfield_cast": (_i, [_vp, _i, _i, _d, _vp, _vp, _i, _vp, _i, _vp, _d, _i, _d, _d, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sr_heightfield_shadow": (_i, [_vp, _i, _i, _d, _vp, _vp, _i, _vp, _d, _vp, _vp]),
+    "sr_orthorectify_scratch": (_i, [_i, _i, C.POINTER(_i64)]),
+    "sr_orthorectify": (_i, [_vp, _i, _i, _d, _d, _d, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _d, _i, _vp, _i64, _vp, _vp, _vp,
+                             _vp, _vp, _vp]),
     "sr_cloud_grid_scratch": (_i, [_i64, _i, _i, C.POINTER(_i64)]),
     "sr_cloud_grid": (_i, [_vp, _vp, _vp, _i64, _d, _d, _d, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i, _vp]),
     "sr_dsm_register_scratch": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i64), C.POINTER(_i)]),

@@ -518,3 +518,99 @@ def sun_visibility_from_dsm(dsm, rays, depth, center, scene_range, max_alt, sun_
     hit = cast_rays(dsm, sr, center, scene_range)["hit"]
     lit = torch.where(hit, 0.0, 1.0).to(torch.float32)
     return torch.where(valid, lit, torch.full_like(lit, float("nan")))
+
+
+# ---- a view's pixels on the DSM grid ---------------------------------------------------------------------------
+def _ortho_image(image, name="image"):
+    """An (H, W, C) GPU image, uint8 or fp32, C in 1..4; (H, W) gains a channel."""
+    if not torch.is_tensor(image) or image.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{name} must be a uint8 or float32 tensor, got {getattr(image, 'dtype', type(image).__name__)}")
+    if image.dim() == 2:
+        image = image.unsqueeze(-1)
+    if image.dim() != 3 or image.numel() == 0 or not 1 <= image.shape[2] <= 4:
+        raise ValueError(f"{name} must be a non-empty (H, W, C) or (H, W) image with C in 1..4, got {tuple(image.shape)}")
+    if not image.is_cuda:
+        raise ValueError(f"{name} must be a GPU tensor: satnerf_amd has no CPU path")
+    return image.contiguous()
+
+
+def _ortho_args(dsm, mode, bias, zone):
+    """The UTM zone number of the call, after the checks that need no tensor."""
+    if not isinstance(dsm, DSM):
+        raise ValueError(f"dsm must be a DSM (raster, xoff, yoff, resolution, zone), got {type(dsm).__name__}")
+    if mode not in ops.ORTHO_MODES:
+        raise ValueError(f"mode must be one of {sorted(ops.ORTHO_MODES)}, got {mode!r}")
+    if not (math.isfinite(float(bias)) and float(bias) >= 0):
+        raise ValueError(f"bias must be finite and >= 0 metres, got {bias}")
+    if zone is None and not dsm.zone:
+        raise ValueError("the DSM carries no UTM zone: pass zone= explicitly")
+    return _zone_number(dsm.zone if zone is None else zone)
+
+
+def orthorectify(dsm, image, rpc, mode="bilinear", bias=0.0, accelerate=True, zone=None):
+    """One view's pixels on the grid of a DSM taken as geometry (csrc/orthorectify.hip).  Every finite cell's centre at the cell's height
+    is projected through ``rpc`` (an "rpcm"-format dict) into ``image`` ((H, W, C) or (H, W), uint8 -- read as value / 255 -- or fp32, on
+    the GPU; pixel centres at integer (col, row)); the line of sight from the cell (lifted by ``bias`` >= 0 metres) towards the camera is
+    walked through the raster up to its highest cell, the cell itself passed through; a cell that is seen takes the image's colour there
+    by ``mode`` "nearest", "bilinear" or "bicubic" (Keys, a = -0.5; indices clamped to the image).  ``zone`` (1..60 or "17R") defaults
+    to the DSM's.  Returns ``{"color": (ysize, xsize, C) fp32, NaN unless visible, "status": (ysize, xsize) uint8 -- 0 empty cell, 1
+    visible, 2 occluded by the DSM, 3 outside the image --, "colrow": (ysize, xsize, 2) fp64 (col, row), NaN for an empty cell,
+    "visible": (ysize, xsize) bool}``.  ``accelerate=False`` takes the plain walk: the same bits."""
+    number = _ortho_args(dsm, mode, bias, zone)
+    image = _ortho_image(image)
+    hgt = _surface(dsm)
+    with torch.cuda.device(hgt.device):
+        color, status, colrow = ops.orthorectify(hgt, dsm.resolution, dsm.xoff, dsm.yoff, number, rpc, image, mode=mode, bias=float(bias),
+                                                 accelerate=accelerate)
+    return {"color": color, "status": status, "colrow": colrow, "visible": status == 1}
+
+
+def ortho_mosaic(dsm, views, mode="bilinear", bias=0.0, min_views=1, accelerate=True, zone=None):
+    """The mean colour of several views on a DSM's grid: :func:`orthorectify` of every ``(image, rpc)`` of ``views`` (images with the same
+    channel count), accumulated per cell over the views that see it, in the order given and without atomics: bitwise repeatable.
+    Returns ``{"color": (ysize, xsize, C) fp32 = fp64 sum / count rounded once, NaN where fewer than ``min_views`` views see the cell,
+    "count": (ysize, xsize) int32 = the views that see each cell}``: the footprint and coverage mask of the imagery on this grid."""
+    number = _ortho_args(dsm, mode, bias, zone)
+    if int(min_views) < 1:
+        raise ValueError(f"min_views must be >= 1, got {min_views}")
+    views = list(views)
+    if not views:
+        raise ValueError("views is empty: a mosaic needs at least one (image, rpc)")
+    views = [(_ortho_image(image, f"views[{k}] image"), rpc) for k, (image, rpc) in enumerate(views)]
+    hgt = _surface(dsm)
+    channels = views[0][0].shape[2]
+    if any(image.shape[2] != channels for image, _ in views):
+        raise ValueError(f"the views' images must have the same channel count, got {[int(image.shape[2]) for image, _ in views]}")
+    ysize, xsize = hgt.shape
+    with torch.cuda.device(hgt.device):
+        total = torch.zeros(ysize, xsize, channels, dtype=torch.float64, device=hgt.device)
+        count = torch.zeros(ysize, xsize, dtype=torch.int32, device=hgt.device)
+        maxima = ops.heightfield_blockmax(hgt)
+        scratch = torch.empty(ops.orthorectify_scratch(xsize, ysize), dtype=torch.uint8, device=hgt.device)
+        bufs = None
+        for image, rpc in views:
+            bufs = ops.orthorectify(hgt, dsm.resolution, dsm.xoff, dsm.yoff, number, rpc, image, mode=mode, bias=float(bias),
+                                    accelerate=accelerate, maxima=maxima, scratch=scratch, sum=total, count=count,
+                                    **({} if bufs is None else dict(color=bufs[0], status=bufs[1], colrow=bufs[2])))
+        mean = (total / count.unsqueeze(-1).to(torch.float64)).to(torch.float32)
+        mean = torch.where((count >= int(min_views)).unsqueeze(-1), mean, torch.full_like(mean, float("nan")))
+    return {"color": mean, "count": count}
+
+
+def orthorectify_dataset(dsm, root_dir, img_dir, split="train", img_downscale=1.0, reader=None, **kw):
+    """:func:`ortho_mosaic` of a dataset's split: the images ``data.load_rays`` and ``data.load_colors`` share (``train.txt`` /
+    ``test.txt`` under ``root_dir``, pixels under ``img_dir``, ``reader`` as in ``data.load_colors``), each at its down-scaled size with
+    its RPC rescaled by ``1 / img_downscale`` (``data.rescale_rpc``).  ``**kw`` goes to :func:`ortho_mosaic`."""
+    from .data import _split_images, load_colors, rescale_rpc
+
+    if not (isinstance(dsm, DSM) and torch.is_tensor(dsm.dsm)):
+        raise ValueError(f"dsm must be a DSM (raster, xoff, yoff, resolution, zone), got {type(dsm).__name__}")
+    metas, _ = _split_images(root_dir, split, img_downscale)
+    rgbs = load_colors(root_dir, img_dir, split=split, img_downscale=img_downscale, device=dsm.dsm.device, reader=reader)
+    views, off = [], 0
+    for k, (d, h, w) in enumerate(metas):
+        rows = rgbs[off:off + h * w] if split == "train" else rgbs[k]
+        off += h * w
+        if h * w:  # an image whose down-scaled grid is empty has no pixel to bring
+            views.append((rows.view(h, w, 3), rescale_rpc(d["rpc"], 1.0 / img_downscale)))
+    return ortho_mosaic(dsm, views, **kw)

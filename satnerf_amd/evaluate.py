@@ -51,6 +51,24 @@ def evaluate_image(models, rays, ts, rgbs, h, w, args, center=None, scene_range=
     return {"typ": out["typ"], "psnr": p, "ssim": s, "mae": mae, "outputs": out}
 
 
+def ortho_psnr(rgb, mosaic, min_views=1):
+    """``metrics.psnr`` of a rendered ortho image against the imagery brought onto the same grid: ``rgb`` ((ysize, xsize, C) or
+    (ysize * xsize, C), e.g. ``render_ortho_dsm``'s ``outputs["rgb"]``) against ``mosaic["color"]`` (``dsm.ortho_mosaic``'s dict) over
+    the cells that at least ``min_views`` views see and where both colours are finite.  A 0-dim fp32 device tensor; NaN when no cell
+    qualifies."""
+    want, count = mosaic["color"], mosaic["count"]
+    if not (torch.is_tensor(rgb) and rgb.is_cuda and torch.is_tensor(want) and want.is_cuda):
+        raise ValueError("ortho_psnr: rgb and the mosaic must live on the GPU; satnerf_amd has no CPU path")
+    if int(min_views) < 1:
+        raise ValueError(f"ortho_psnr: min_views must be >= 1, got {min_views}")
+    if rgb.numel() != want.numel() or rgb.shape[-1] != want.shape[-1]:
+        raise ValueError(f"ortho_psnr: rgb {tuple(rgb.shape)} does not hold the mosaic's {tuple(want.shape)} colours")
+    pred = rgb.reshape(want.shape).float()
+    valid = (count >= int(min_views)) & torch.isfinite(want).all(-1) & torch.isfinite(pred).all(-1)
+    keep = valid.unsqueeze(-1)
+    return metrics.psnr(torch.where(keep, pred, 0.0), torch.where(keep, want, 0.0), valid_mask=valid)
+
+
 def solar_incidence_angle(sun_d):
     """The angle in degrees between a sun direction and the vertical, in fp64: arccos of the z component of the normalised direction.
     study_solar_interpolation.py:155-159 and :193-196 take the dot product with the unit normal (0, 0, 1), which adds two exact zeros to

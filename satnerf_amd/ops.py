@@ -1189,6 +1189,69 @@ def heightfield_shadow(hgt, resolution, sun_d, bias=0.0, accelerate=True, maxima
     return out
 
 
+# ---- orthorectification onto a DSM raster (csrc/orthorectify.hip) ------------------------------------------------------------------
+ORTHO_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+ORTHO_STAGES = {"all": 0, "project": 1, "sample": 2}
+
+
+def orthorectify_scratch(xsize, ysize):
+    """Bytes of scratch sr_orthorectify needs for an (ysize, xsize) raster (host only)."""
+    return _scratch_bytes("sr_orthorectify_scratch", xsize, ysize)
+
+
+def orthorectify(hgt, resolution, xoff, yoff, zone, rpc, image, mode="bilinear", bias=0.0, accelerate=True, maxima=None, scratch=None,
+                 color=None, status=None, colrow=None, sum=None, count=None, stage="all"):
+    """sr_orthorectify: one view brought onto the (ysize, xsize) fp32 device raster ``hgt`` placed at ``xoff`` / ``yoff`` in UTM ``zone``
+    (1..60).  ``rpc``: an "rpcm"-format dict; ``image``: (H, W, C) device tensor, uint8 (values / 255) or fp32, C in 1..4, unit channel
+    stride.  Returns (color (ysize, xsize, C) fp32, NaN where the cell is not visible; status (ysize, xsize) uint8: 0 empty, 1 visible,
+    2 occluded, 3 outside the image; colrow (ysize, xsize, 2) fp64).  ``sum`` (ysize, xsize, C) fp64 and ``count`` (ysize, xsize) int32:
+    accumulators every visible cell adds its colour and 1 to, both or neither.  ``maxima``: heightfield_blockmax's pair when at hand.
+    ``scratch``: a contiguous device tensor of at least orthorectify_scratch bytes.  ``stage``: "all", or "project" / "sample" for one of
+    the two launches ("sample" reads the ``colrow`` and ``scratch`` a "project" call left).  Nothing is read back."""
+    if mode not in ORTHO_MODES:
+        raise ValueError(f"mode must be one of {sorted(ORTHO_MODES)}, got {mode!r}")
+    if stage not in ORTHO_STAGES:
+        raise ValueError(f"stage must be one of {sorted(ORTHO_STAGES)}, got {stage!r}")
+    hgt, xsize, ysize = _heightfield(hgt)
+    if not (torch.is_tensor(image) and image.is_cuda):
+        raise ValueError("image must live on the GPU; satnerf_amd has no CPU path")
+    _same_device(image, "image")
+    if image.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"image must be uint8 or float32 (got {image.dtype})")
+    if image.dim() != 3 or image.numel() == 0 or not 1 <= image.shape[2] <= 4:
+        raise ValueError(f"image must be a non-empty (H, W, C) tensor with C in 1..4, got {tuple(image.shape)}")
+    height, width, channels = (int(v) for v in image.shape)
+    pix_stride = image.stride(1) if width > 1 else channels  # the stride of a dimension of size 1 says nothing
+    row_stride = image.stride(0) if height > 1 else width * pix_stride
+    if (image.stride(2) != 1 and channels > 1) or pix_stride < channels or row_stride < (width - 1) * pix_stride + channels:
+        raise ValueError(f"image must have unit channel stride and rows and pixels that do not overlap, got strides {image.stride()}")
+    if not (float(bias) >= 0 and float(bias) != float("inf")):
+        raise ValueError(f"bias must be finite and >= 0 metres, got {bias}")
+    if (sum is None) != (count is None):
+        raise ValueError("give both accumulators, sum and count, or neither")
+    buf = rpc_buffer(rpc)
+    dev = hgt.device
+    blockmax, gmax = _heightfield_maxima(hgt, accelerate, maxima, always=True)
+    scratch = _metric_scratch(scratch, orthorectify_scratch(xsize, ysize), dev)
+
+    def out(t, name, shape, dtype):
+        t = torch.empty(shape, dtype=dtype, device=dev) if t is None else _chk(t, name, dtype)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+        return t
+
+    color = out(color, "color", (ysize, xsize, channels), torch.float32)
+    status = out(status, "status", (ysize, xsize), torch.uint8)
+    colrow = out(colrow, "colrow", (ysize, xsize, 2), torch.float64)
+    if sum is not None:
+        sum, count = out(sum, "sum", (ysize, xsize, channels), torch.float64), out(count, "count", (ysize, xsize), torch.int32)
+    _lib.call("sr_orthorectify", _p(hgt), xsize, ysize, float(resolution), float(xoff), float(yoff), int(zone), _p(blockmax), _p(gmax),
+              int(bool(accelerate)), C.addressof(buf), _p(image), 0 if image.dtype == torch.uint8 else 1, width, height, channels,
+              int(row_stride), int(pix_stride), ORTHO_MODES[mode], float(bias), ORTHO_STAGES[stage], _p(scratch),
+              scratch.numel() * scratch.element_size(), _p(color), _p(status), _p(colrow), _p(sum), _p(count), _stream())
+    return color, status, colrow
+
+
 # ---- cloud fusion (csrc/cloud_grid.hip) --------------------------------------------------------------------------------------------
 CLOUD_RULES ={"nearest": 0, "floor": 1}
 CLOUD_MODES = {"min": 0, "max": 1, "avg": 2, "med": 3}
