@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SR_VERSION 100 /* major*10000 + minor*100 + patch */
+#define SR_VERSION 200 /* major*10000 + minor*100 + patch; while major is 0 an incompatible signature change bumps minor */
 
 /* numeric modes of the fused MLP (SURVEY.md section 7 "Hard parts") */
 #define SR_MODE_BF16 1   /* single-pass bf16 MFMA, fp32 accumulate -- throughput mode            */
@@ -303,39 +303,68 @@ int sr_render_loss(const float* z_vals, const float* sigma, const float* noise, 
  * replays: [0] 1-based optimizer step (ticked by sr_pack_all), [1] learning rate (sr_adam_step_graph with lr < 0 reads it:
  * StepLR(gamma 0.9) per epoch, main.py:86-94 / train_utils.py:41-57), [2] != 0 while the SNerfLoss warm-up lasts (the colour loss
  * is then the plain MSE of metrics.SNerfLoss, main.py:128-131 -- no beta term, no beta gradient), [3] reserved.
- * sr_grad_tail = sr_unpack_grads + sr_sky_bwd + sr_embedding_bwd as three block ranges of one launch (training fast path;
- * n_blocks = rows of the planned job table `blocks`);
  * sr_adam_step_graph = sr_adam_step with the 1-based step count read from the device (state[0], advanced by sr_pack_all's
  * `tick` earlier in the same step) so the launch can be replayed from a hipGraph. */
-int sr_grad_tail(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                 float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden,
-                 const float* w1, const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1,
-                 float* g_w2, float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, void* stream);
-/* sr_grad_tail + sr_adam_step_graph in one launch (the single-GPU captured step): the thread that reduces a parameter's slices applies
- * torch.optim.Adam to it (params / exp_avg / exp_avg_sq are aligned with grad: element i of all four is parameter i) and zeroes its
- * gradient slot; `late_idx` (n_late flat indices relative to grad) lists the parameters whose gradients arrive by atomics -- the sky head
- * and the embedding rows: the last atomics block to finish updates them.  `state` = the 4-float schedule block ([0] 1-based step, [1]
- * rate used when lr < 0, [3] arrival counter, zero between launches).
- * `pack` (NULL or pack->map == NULL: none), r05: the launch ALSO keeps the weight streams current -- the thread that updated parameter i
- * writes it to its (at most two) places in the packed streams, so the next step needs no sr_pack_all launch.  map = 2 int32 per
- * parameter (packing.pack_scatter_map): position | scale index << 26 | (1 << 28: the fp32 fc_net.0 table `l0`), -1 = none; positions
- * address `hi` (bf16; fp16 below n_f16 as sr_pack_all's n_f16) and, if not NULL, `lo` (the bf16x3 remainder plane); the value written
- * is param * scales[index], the element-wise arithmetic of sr_pack_all: the streams hold the same bits as a fresh sr_pack_all. */
+/* `pack` of the launches that also keep the weight streams current (r05; NULL or pack->map == NULL: none): the thread that updated
+ * parameter i writes it to its (at most two) places in the packed streams, so the next step needs no sr_pack_all launch.  The value
+ * written is param * scales[index], the element-wise arithmetic of sr_pack_all: the streams hold the same bits as a fresh sr_pack_all. */
 typedef struct sr_pack_scatter {
-  const int32_t* map;
-  uint16_t* hi;
-  uint16_t* lo;
-  float* l0;
-  int64_t n_f16;
+  const int32_t* map; /* 2 int32 per parameter (packing.pack_scatter_map): position | scale index << 26 | (1 << 28: the fp32 table `l0`), -1 = none */
+  uint16_t* hi;       /* the stream the positions address: bf16; fp16 below n_f16 */
+  uint16_t* lo;       /* the bf16x3 remainder plane, or NULL */
+  float* l0;          /* the fp32 fc_net.0 table */
+  int64_t n_f16;      /* as sr_pack_all's n_f16 */
   float scales[4];
 } sr_pack_scatter;
-int sr_grad_tail_adam(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                      float* grad,
-                      int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1, const float* b1,
-                      const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2, float* g_b2,
-                      const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params, float* exp_avg,
-                      float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1, float beta2, float eps,
-                      float grad_scale, const sr_pack_scatter* pack, void* stream);
+/* The gradient tail, the last launch of a training step: sr_unpack_grads + sr_sky_bwd + sr_embedding_bwd as three block ranges of ONE
+ * launch.  sr_grad_tail_args holds what its four entries share. */
+typedef struct sr_grad_tail_args {
+  const float* partial;  /* the split-K slices sr_satnerf_wgrad[8] wrote */
+  const int32_t* gidx;   /* (n_params) as sr_unpack_grads: where parameter i's sum lives in a slice; < 0 = no weight-gradient GEMM produces it */
+  const float* gscale;   /* (n_params) as sr_unpack_grads: the factor on parameter i's sum */
+  int64_t n_params;
+  const int32_t* blocks; /* the planned job table (sr_wgrad_plan), device */
+  int n_blocks;          /* its rows, >= 1 */
+  float* grad;           /* (n_params) flat gradient buffer */
+  int accumulate;        /* != 0: add to what `grad` holds (the solar-correction / depth-supervision passes of the step), 0: overwrite */
+  const float* sun;      /* (n_rays, >= 3) sun directions of the batch, the sky head's input (sr_sky_bwd) */
+  int sun_stride;        /* row stride of `sun` in floats */
+  int64_t n_rays;        /* rays of the batch; <= 0: nothing is launched */
+  int hidden;            /* width of the sky head */
+  const float* w1;       /* sky head: (hidden, 3) */
+  const float* b1;       /*           (hidden)    */
+  const float* w2;       /*           (3, hidden) */
+  const float* sky;      /* (n_rays, 3) the head's output */
+  const float* d_sky;    /* (n_rays, 3) its gradient */
+  float* g_w1;           /* the head's parameter gradients, added to (atomics, or in a fixed order by the _det entries) */
+  float* g_b1;
+  float* g_w2;
+  float* g_b2;
+  const float* d_t;      /* (n_rays * n_samples, tau) gradient w.r.t. each point's embedding vector (sr_satnerf_mlp_bwd) */
+  const int64_t* ts;     /* (n_rays) embedding row of each ray */
+  int n_samples;
+  int tau;
+  float* g_emb;          /* (rows, tau) g_emb[ts[r]] += sum_j d_t[r * n_samples + j] (sr_embedding_bwd) */
+} sr_grad_tail_args;
+/* The optimizer half of sr_grad_tail_adam[_det] = sr_grad_tail + sr_adam_step_graph in one launch (the single-GPU captured step): the
+ * thread that reduces a parameter's slices applies torch.optim.Adam to it and zeroes its gradient slot. */
+typedef struct sr_tail_adam_args {
+  float* params;           /* flat buffers aligned with `grad`: element i of all four is parameter i */
+  float* exp_avg;
+  float* exp_avg_sq;
+  const int32_t* late_idx; /* (n_late) flat indices relative to `grad` of the parameters whose gradients arrive from OTHER blocks (the sky head,
+                              the embedding rows): the last of those blocks to finish updates them */
+  int n_late;              /* >= 0; late_idx may be NULL only when it is 0 */
+  float* state;            /* the 4-float schedule block: [0] 1-based step, [1] rate used when lr < 0, [3] arrival counter, zero between launches */
+  float lr;                /* < 0: read state[1] */
+  float beta1;
+  float beta2;
+  float eps;
+  float grad_scale;
+  const sr_pack_scatter* pack; /* NULL or pack->map == NULL: none; pack->map holds n_params x 2 words */
+} sr_tail_adam_args;
+int sr_grad_tail(const sr_grad_tail_args* args, void* stream);
+int sr_grad_tail_adam(const sr_grad_tail_args* args, const sr_tail_adam_args* adam, void* stream);
 int sr_adam_step_graph(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                        float beta2, float eps, float grad_scale, float* state, int zero_grad, void* stream);
 
@@ -370,17 +399,8 @@ int sr_sky_bwd_det(const float* sun, int sun_stride, int64_t n, int hidden, cons
                    int64_t scratch_bytes, void* stream);
 int sr_embedding_bwd_det(const float* d_t, const int64_t* ts, int64_t n_rays, int n_samples, int tau, float* g_emb, float* scratch,
                          int64_t scratch_bytes, void* stream);
-int sr_grad_tail_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                     float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden,
-                     const float* w1, const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1,
-                     float* g_w2, float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* scratch,
-                     int64_t scratch_bytes, void* stream);
-int sr_grad_tail_adam_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                          float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
-                          const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                          float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params,
-                          float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1,
-                          float beta2, float eps, float grad_scale, const sr_pack_scatter* pack, float* scratch, int64_t scratch_bytes,
+int sr_grad_tail_det(const sr_grad_tail_args* args, float* scratch, int64_t scratch_bytes, void* stream);
+int sr_grad_tail_adam_det(const sr_grad_tail_args* args, const sr_tail_adam_args* adam, float* scratch, int64_t scratch_bytes,
                           void* stream);
 /* sr_adam_step_graph that also re-packs (r06: the data-parallel step = the single-GPU step + one collective): Adam on all n elements of
  * the flat buffers, and each of the first n_packed parameters (the coarse model's; `pack->map` holds n_packed x 2 words) written into its

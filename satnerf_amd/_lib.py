@@ -44,6 +44,18 @@ class PackScatter(C.Structure):
     _fields_ = [("map", _vp), ("hi", _vp), ("lo", _vp), ("l0", _vp), ("n_f16", _i64), ("scales", _f * 4)]
 
 
+class GradTailArgs(C.Structure):
+    _fields_ = [("partial", _vp), ("gidx", _vp), ("gscale", _vp), ("n_params", _i64), ("blocks", _vp), ("n_blocks", _i), ("grad", _vp),
+                ("accumulate", _i), ("sun", _vp), ("sun_stride", _i), ("n_rays", _i64), ("hidden", _i), ("w1", _vp), ("b1", _vp), ("w2", _vp),
+                ("sky", _vp), ("d_sky", _vp), ("g_w1", _vp), ("g_b1", _vp), ("g_w2", _vp), ("g_b2", _vp), ("d_t", _vp), ("ts", _vp),
+                ("n_samples", _i), ("tau", _i), ("g_emb", _vp)]
+
+
+class TailAdamArgs(C.Structure):
+    _fields_ = [("params", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("late_idx", _vp), ("n_late", _i), ("state", _vp), ("lr", _f),
+                ("beta1", _f), ("beta2", _f), ("eps", _f), ("grad_scale", _f), ("pack", C.POINTER(PackScatter))]
+
+
 class LinearSrc(C.Structure):
     _fields_ = [("x", _vp), ("ld", _i), ("k", _i), ("act", _i), ("w0", _f), ("row_div", _i)]
 
@@ -95,19 +107,15 @@ SIGNATURES = {
     "sr_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i64, _i, _vp]),
     "sr_gather_setup": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _i, _vp]),
     "sr_gather_batch": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "sr_grad_tail": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
-                          _vp, _vp]),
-    "sr_grad_tail_adam": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
-                               _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
+    "sr_grad_tail": (_i, [C.POINTER(GradTailArgs), _vp]),
+    "sr_grad_tail_adam": (_i, [C.POINTER(GradTailArgs), C.POINTER(TailAdamArgs), _vp]),
     "sr_adam_step_graph": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _vp, _i, _vp]),
     # the fixed-order twins: their atomic twin's arguments, then (scratch, scratch_bytes) in front of the stream
     "sr_late_grad_scratch_bytes": (_i64, [_i64, _i, _i]),
     "sr_sky_bwd_det": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sr_embedding_bwd_det": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp]),
-    "sr_grad_tail_det": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
-                              _vp, _vp, _i64, _vp]),
-    "sr_grad_tail_adam_det": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                   _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _vp, _i64, _vp]),
+    "sr_grad_tail_det": (_i, [C.POINTER(GradTailArgs), _vp, _i64, _vp]),
+    "sr_grad_tail_adam_det": (_i, [C.POINTER(GradTailArgs), C.POINTER(TailAdamArgs), _vp, _i64, _vp]),
     "sr_adam_step_pack": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _vp, _i, _i64, _vp, _vp]),
     "sr_pack_all": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sr_gather_scale_f32": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),

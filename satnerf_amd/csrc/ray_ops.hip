@@ -1071,100 +1071,58 @@ extern "C" int sr_sky_bwd_det(const float* sun, int sun_stride, int64_t n, int h
   return check_launch("sky_bwd_det_kernel");
 }
 
-static int grad_tail_fill(const char* who, GradTailParams& q, const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params,
-                          const int32_t* blocks, int n_blocks, float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden,
-                          const float* w1, const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                          float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb) {
-  SR_REQUIRE(partial && gidx && gscale && blocks && grad && sun && w1 && b1 && w2 && sky && d_sky && g_w1 && g_b1 && g_w2 && g_b2 && d_t && ts && g_emb,
+// The one host path of the four gradient-tail entries (`who`: the entry's name, for the messages): `adam` selects the launches that also
+// update, `scratch` the fixed-order ones.  The public structs are copied field by field into the kernels' parameter blocks.
+static int grad_tail_launch(const char* who, const sr_grad_tail_args* t, const sr_tail_adam_args* o, bool adam, float* scratch, int64_t scratch_bytes,
+                            bool det, void* stream) {
+  SR_REQUIRE(t != nullptr && (o != nullptr || !adam), "%s: null argument struct", who);
+  SR_REQUIRE(t->partial && t->gidx && t->gscale && t->blocks && t->grad && t->sun && t->w1 && t->b1 && t->w2 && t->sky && t->d_sky && t->g_w1 && t->g_b1 &&
+                 t->g_w2 && t->g_b2 && t->d_t && t->ts && t->g_emb,
              "%s: null pointer", who);
-  SR_REQUIRE(n_blocks >= 1, "%s: n_blocks = %d", who, n_blocks);
-  q.partial = partial, q.gidx = gidx, q.gscale = gscale, q.n_params = n_params, q.blocks = blocks, q.grad = grad;
-  q.accumulate = accumulate, q.sun = sun, q.sun_stride = sun_stride, q.n_rays = n_rays, q.hidden = hidden, q.w1 = w1, q.b1 = b1, q.w2 = w2;
-  q.sky = sky, q.d_sky = d_sky, q.g_w1 = g_w1, q.g_b1 = g_b1, q.g_w2 = g_w2, q.g_b2 = g_b2, q.d_t = d_t, q.ts = (const long long*)ts;
-  q.S = n_samples, q.tau = tau, q.g_emb = g_emb, q.n_blocks = n_blocks;
-  q.blocks_unpack = (int)((n_params + 255) / 256);
-  q.blocks_sky = (int)((n_rays + kSkyRays - 1) / kSkyRays);
-  q.blocks_emb = (int)((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
-  return 0;
-}
-
-extern "C" int sr_grad_tail(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                            float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
-                            const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                            float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, void* stream) {
-  GradTailParams q;
-  if (grad_tail_fill("sr_grad_tail", q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1, b1, w2,
-                     sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
-    return 1;
-  if (n_rays <= 0) return 0;
-  hipLaunchKernelGGL(grad_tail_kernel, dim3(q.blocks_unpack + q.blocks_sky + q.blocks_emb), dim3(256), 0, (hipStream_t)stream, q);
-  return check_launch("grad_tail_kernel");
-}
-
-extern "C" int sr_grad_tail_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                                float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
-                                const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                                float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* scratch,
-                                int64_t scratch_bytes, void* stream) {
-  GradTailParams q;
-  if (grad_tail_fill("sr_grad_tail_det", q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1, b1,
-                     w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
-    return 1;
-  if (n_rays <= 0) return 0;
-  LateScratch d;
-  if (late_scratch_checked("sr_grad_tail_det", scratch, scratch_bytes, n_rays, hidden, n_rays, tau, &d)) return 1;
-  hipLaunchKernelGGL(grad_tail_det_kernel, dim3(q.blocks_unpack + q.blocks_sky + q.blocks_emb), dim3(256), 0, (hipStream_t)stream, q, d);
-  return check_launch("grad_tail_det_kernel");
-}
-
-static int tail_adam_fill(const char* who, TailAdamParams& a, float* params, float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late,
-                          float* state, float lr, float beta1, float beta2, float eps, float grad_scale, const sr_pack_scatter* pack) {
-  a.p = params, a.m = exp_avg, a.v = exp_avg_sq, a.late = late_idx, a.n_late = n_late, a.state = state;
-  a.arrive = reinterpret_cast<unsigned*>(state + 3);  // the schedule block's arrival counter (ray_device.h tick_when_all_read: unused by training steps)
-  a.lr = lr, a.b1 = beta1, a.b2 = beta2, a.eps = eps, a.grad_scale = grad_scale;
-  a.pack = sr_pack_scatter{};
-  if (pack != nullptr && pack->map != nullptr) {
-    SR_REQUIRE(pack->hi && pack->l0 && pack->n_f16 >= 0, "%s: pack needs the stream and the fc_net.0 table", who);
-    a.pack = *pack;
+  SR_REQUIRE(t->n_blocks >= 1, "%s: n_blocks = %d", who, t->n_blocks);
+  if (adam)
+    SR_REQUIRE(o->params && o->exp_avg && o->exp_avg_sq && o->state && (o->late_idx || o->n_late == 0) && o->n_late >= 0, "%s: null optimizer pointer", who);
+  if (t->n_rays <= 0) return 0;
+  TailAdamParams a;
+  GradTailParams& q = a.q;
+  q.partial = t->partial, q.gidx = t->gidx, q.gscale = t->gscale, q.n_params = t->n_params, q.blocks = t->blocks, q.grad = t->grad;
+  q.accumulate = t->accumulate, q.sun = t->sun, q.sun_stride = t->sun_stride, q.n_rays = t->n_rays, q.hidden = t->hidden, q.w1 = t->w1, q.b1 = t->b1;
+  q.w2 = t->w2, q.sky = t->sky, q.d_sky = t->d_sky, q.g_w1 = t->g_w1, q.g_b1 = t->g_b1, q.g_w2 = t->g_w2, q.g_b2 = t->g_b2, q.d_t = t->d_t;
+  q.ts = (const long long*)t->ts, q.S = t->n_samples, q.tau = t->tau, q.g_emb = t->g_emb, q.n_blocks = t->n_blocks;
+  q.blocks_unpack = (int)((t->n_params + 255) / 256);
+  q.blocks_sky = (int)((t->n_rays + kSkyRays - 1) / kSkyRays);
+  q.blocks_emb = (int)((t->n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
+  if (adam) {
+    a.p = o->params, a.m = o->exp_avg, a.v = o->exp_avg_sq, a.late = o->late_idx, a.n_late = o->n_late, a.state = o->state;
+    a.arrive = reinterpret_cast<unsigned*>(o->state + 3);  // the schedule block's arrival counter (ray_device.h tick_when_all_read: unused by training steps)
+    a.lr = o->lr, a.b1 = o->beta1, a.b2 = o->beta2, a.eps = o->eps, a.grad_scale = o->grad_scale;
+    a.pack = sr_pack_scatter{};
+    if (o->pack != nullptr && o->pack->map != nullptr) {
+      SR_REQUIRE(o->pack->hi && o->pack->l0 && o->pack->n_f16 >= 0, "%s: pack needs the stream and the fc_net.0 table", who);
+      a.pack = *o->pack;
+    }
   }
-  return 0;
-}
-
-extern "C" int sr_grad_tail_adam(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                                 float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
-                                 const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                                 float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params,
-                                 float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1,
-                                 float beta2, float eps, float grad_scale, const sr_pack_scatter* pack, void* stream) {
-  TailAdamParams a;
-  if (grad_tail_fill("sr_grad_tail_adam", a.q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1, b1,
-                     w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
-    return 1;
-  SR_REQUIRE(params && exp_avg && exp_avg_sq && state && (late_idx || n_late == 0) && n_late >= 0, "sr_grad_tail_adam: null optimizer pointer");
-  if (n_rays <= 0) return 0;
-  if (tail_adam_fill("sr_grad_tail_adam", a, params, exp_avg, exp_avg_sq, late_idx, n_late, state, lr, beta1, beta2, eps, grad_scale, pack)) return 1;
-  hipLaunchKernelGGL(grad_tail_adam_kernel, dim3(a.q.blocks_unpack + a.q.blocks_sky + a.q.blocks_emb), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("grad_tail_adam_kernel");
-}
-
-extern "C" int sr_grad_tail_adam_det(const float* partial, const int32_t* gidx, const float* gscale, int64_t n_params, const int32_t* blocks, int n_blocks,
-                                     float* grad, int accumulate, const float* sun, int sun_stride, int64_t n_rays, int hidden, const float* w1,
-                                     const float* b1, const float* w2, const float* sky, const float* d_sky, float* g_w1, float* g_b1, float* g_w2,
-                                     float* g_b2, const float* d_t, const int64_t* ts, int n_samples, int tau, float* g_emb, float* params,
-                                     float* exp_avg, float* exp_avg_sq, const int32_t* late_idx, int n_late, float* state, float lr, float beta1,
-                                     float beta2, float eps, float grad_scale, const sr_pack_scatter* pack, float* scratch, int64_t scratch_bytes,
-                                     void* stream) {
-  TailAdamParams a;
-  if (grad_tail_fill("sr_grad_tail_adam_det", a.q, partial, gidx, gscale, n_params, blocks, n_blocks, grad, accumulate, sun, sun_stride, n_rays, hidden, w1,
-                     b1, w2, sky, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_samples, tau, g_emb))
-    return 1;
-  SR_REQUIRE(params && exp_avg && exp_avg_sq && state && (late_idx || n_late == 0) && n_late >= 0, "sr_grad_tail_adam_det: null optimizer pointer");
-  if (n_rays <= 0) return 0;
-  if (tail_adam_fill("sr_grad_tail_adam_det", a, params, exp_avg, exp_avg_sq, late_idx, n_late, state, lr, beta1, beta2, eps, grad_scale, pack)) return 1;
   LateScratch d;
-  if (late_scratch_checked("sr_grad_tail_adam_det", scratch, scratch_bytes, n_rays, hidden, n_rays, tau, &d)) return 1;
-  hipLaunchKernelGGL(grad_tail_adam_det_kernel, dim3(a.q.blocks_unpack + a.q.blocks_sky + a.q.blocks_emb), dim3(256), 0, (hipStream_t)stream, a, d);
-  return check_launch("grad_tail_adam_det_kernel");
+  if (det && late_scratch_checked(who, scratch, scratch_bytes, t->n_rays, t->hidden, t->n_rays, t->tau, &d)) return 1;
+  const dim3 grid(q.blocks_unpack + q.blocks_sky + q.blocks_emb), block(256);
+  if (adam && det) hipLaunchKernelGGL(grad_tail_adam_det_kernel, grid, block, 0, (hipStream_t)stream, a, d);
+  else if (adam) hipLaunchKernelGGL(grad_tail_adam_kernel, grid, block, 0, (hipStream_t)stream, a);
+  else if (det) hipLaunchKernelGGL(grad_tail_det_kernel, grid, block, 0, (hipStream_t)stream, q, d);
+  else hipLaunchKernelGGL(grad_tail_kernel, grid, block, 0, (hipStream_t)stream, q);
+  return check_launch(adam ? (det ? "grad_tail_adam_det_kernel" : "grad_tail_adam_kernel") : det ? "grad_tail_det_kernel" : "grad_tail_kernel");
+}
+
+extern "C" int sr_grad_tail(const sr_grad_tail_args* args, void* stream) {
+  return grad_tail_launch("sr_grad_tail", args, nullptr, false, nullptr, 0, false, stream);
+}
+extern "C" int sr_grad_tail_det(const sr_grad_tail_args* args, float* scratch, int64_t scratch_bytes, void* stream) {
+  return grad_tail_launch("sr_grad_tail_det", args, nullptr, false, scratch, scratch_bytes, true, stream);
+}
+extern "C" int sr_grad_tail_adam(const sr_grad_tail_args* args, const sr_tail_adam_args* adam, void* stream) {
+  return grad_tail_launch("sr_grad_tail_adam", args, adam, true, nullptr, 0, false, stream);
+}
+extern "C" int sr_grad_tail_adam_det(const sr_grad_tail_args* args, const sr_tail_adam_args* adam, float* scratch, int64_t scratch_bytes, void* stream) {
+  return grad_tail_launch("sr_grad_tail_adam_det", args, adam, true, scratch, scratch_bytes, true, stream);
 }
 
 extern "C" int sr_adam_step_pack(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,

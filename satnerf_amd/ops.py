@@ -856,13 +856,32 @@ def gather_setup(rays, rgbs, ts, idx, out, n_samples, w1, b1, w2, b2, z, sky_rgb
               _p(_chk(step_counter, "step_counter", allow_none=True)), int(step_offset), _stream())
 
 
+def _grad_tail_args(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays, n_samples, tau,
+                    g_emb):
+    """The sr_grad_tail_args of the four tail wrappers (their first 21 arguments); it holds addresses only: the tensors are the caller's."""
+    sun, stride = _rows(sun, "sun", 3)
+    return _lib.GradTailArgs(
+        partial=_p(partial), gidx=_p(_chk(gidx, "gidx", torch.int32)), gscale=_p(_chk(gscale, "gscale")), n_params=gidx.numel(), blocks=_p(plan),
+        n_blocks=plan.shape[0], grad=_p(_chk(grad_flat, "grad_flat")), accumulate=1, sun=_p(sun), sun_stride=stride, n_rays=n_rays,
+        hidden=w1.shape[0], w1=_p(w1), b1=_p(b1), w2=_p(w2), sky=_p(_chk(sky_rgb, "sky")), d_sky=_p(_chk(d_sky, "d_sky")), g_w1=_p(g_w1),
+        g_b1=_p(g_b1), g_w2=_p(g_w2), g_b2=_p(g_b2), d_t=_p(_chk(d_t, "d_t")), ts=_p(_chk(ts, "ts", torch.int64)), n_samples=n_samples, tau=tau,
+        g_emb=_p(_chk(g_emb, "g_emb")))
+
+
+def _tail_adam_args(n_params, params, exp_avg, exp_avg_sq, late_idx, state, lr, betas, eps, grad_scale, pack):
+    """The sr_tail_adam_args of the two tail + Adam wrappers; the struct keeps its PackScatter alive."""
+    ps = C.pointer(_pack_scatter_struct(pack, n_params)) if pack is not None else None
+    return _lib.TailAdamArgs(
+        params=_p(_chk(params, "params")), exp_avg=_p(_chk(exp_avg, "exp_avg")), exp_avg_sq=_p(_chk(exp_avg_sq, "exp_avg_sq")),
+        late_idx=_p(_chk(late_idx, "late_idx", torch.int32)), n_late=late_idx.numel(), state=_p(_chk(state, "state")), lr=float(lr),
+        beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), grad_scale=float(grad_scale), pack=ps)
+
+
 def grad_tail(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
               n_samples, tau, g_emb):
-    sun, stride = _rows(sun, "sun", 3)
-    _lib.call("sr_grad_tail", _p(partial), _p(_chk(gidx, "gidx", torch.int32)), _p(_chk(gscale, "gscale")), gidx.numel(), _p(plan), plan.shape[0],
-              _p(_chk(grad_flat, "grad_flat")), 1, _p(sun), stride, n_rays, w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")),
-              _p(_chk(d_sky, "d_sky")), _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_samples, tau,
-              _p(_chk(g_emb, "g_emb")), _stream())
+    args = _grad_tail_args(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
+                           n_samples, tau, g_emb)
+    _lib.call("sr_grad_tail", C.byref(args), _stream())
 
 
 def grad_tail_adam(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays, n_samples, tau,
@@ -870,19 +889,10 @@ def grad_tail_adam(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_
     """``grad_tail`` + ``adam_step_graph`` in one launch (sr_grad_tail_adam): ``params`` / ``exp_avg`` / ``exp_avg_sq`` are the flat buffers
     aligned with ``grad_flat`` (they may extend past it: ``late_idx`` addresses the embedding rows behind the model's parameters).
     ``pack`` (``SatNeRF.pack_scatter``): the launch also writes every updated parameter into the weight streams (no sr_pack_all next step)."""
-    sun, stride = _rows(sun, "sun", 3)
-    ps = None
-    if pack is not None:
-        if pack["map"].shape != (gidx.numel(), 2):
-            raise ValueError("pack map does not match the parameter count")
-        ps = _lib.PackScatter(_p(_chk(pack["map"], "pack map", torch.int32)), _p(pack["hi"]), _p(pack["lo"]), _p(_chk(pack["l0"], "pack l0")),
-                              int(pack["n_f16"]), (C.c_float * 4)(*[float(x) for x in pack["scales"]]))
-    _lib.call("sr_grad_tail_adam", _p(partial), _p(_chk(gidx, "gidx", torch.int32)), _p(_chk(gscale, "gscale")), gidx.numel(), _p(plan), plan.shape[0],
-              _p(_chk(grad_flat, "grad_flat")), 1, _p(sun), stride, n_rays, w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")),
-              _p(_chk(d_sky, "d_sky")), _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_samples, tau,
-              _p(_chk(g_emb, "g_emb")), _p(_chk(params, "params")), _p(_chk(exp_avg, "exp_avg")), _p(_chk(exp_avg_sq, "exp_avg_sq")),
-              _p(_chk(late_idx, "late_idx", torch.int32)), late_idx.numel(), _p(_chk(state, "state")), float(lr), float(betas[0]), float(betas[1]),
-              float(eps), float(grad_scale), C.byref(ps) if ps is not None else None, _stream())
+    args = _grad_tail_args(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
+                           n_samples, tau, g_emb)
+    adam = _tail_adam_args(gidx.numel(), params, exp_avg, exp_avg_sq, late_idx, state, lr, betas, eps, grad_scale, pack)
+    _lib.call("sr_grad_tail_adam", C.byref(args), C.byref(adam), _stream())
 
 
 # ---- fixed-order sky and embedding gradients (include/satrender.h: the *_det entry points) ---------------------------------------------
@@ -925,11 +935,9 @@ def embedding_bwd_det(d_t, ts, n_rays, n_samples, tau, g_emb, scratch):
 def grad_tail_det(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
                   n_samples, tau, g_emb, scratch):
     """``grad_tail`` whose sky and embedding gradients are summed in a fixed order (sr_grad_tail_det); ``scratch``: ``late_grad_scratch``."""
-    sun, stride = _rows(sun, "sun", 3)
-    _lib.call("sr_grad_tail_det", _p(partial), _p(_chk(gidx, "gidx", torch.int32)), _p(_chk(gscale, "gscale")), gidx.numel(), _p(plan), plan.shape[0],
-              _p(_chk(grad_flat, "grad_flat")), 1, _p(sun), stride, n_rays, w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")),
-              _p(_chk(d_sky, "d_sky")), _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_samples, tau,
-              _p(_chk(g_emb, "g_emb")), *_late_scratch(scratch, late_grad_scratch_bytes(n_rays, w1.shape[0], tau)), _stream())
+    args = _grad_tail_args(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
+                           n_samples, tau, g_emb)
+    _lib.call("sr_grad_tail_det", C.byref(args), *_late_scratch(scratch, late_grad_scratch_bytes(n_rays, w1.shape[0], tau)), _stream())
 
 
 def grad_tail_adam_det(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays, n_samples,
@@ -937,15 +945,11 @@ def grad_tail_adam_det(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, 
                        pack=None):
     """``grad_tail_adam`` whose sky and embedding gradients are summed in a fixed order before the last block updates the ``late_idx``
     parameters (sr_grad_tail_adam_det); ``scratch``: ``late_grad_scratch``.  The arrival counter is ``state[3]``, as in ``grad_tail_adam``."""
-    sun, stride = _rows(sun, "sun", 3)
-    ps = _pack_scatter_struct(pack, gidx.numel()) if pack is not None else None
-    _lib.call("sr_grad_tail_adam_det", _p(partial), _p(_chk(gidx, "gidx", torch.int32)), _p(_chk(gscale, "gscale")), gidx.numel(), _p(plan), plan.shape[0],
-              _p(_chk(grad_flat, "grad_flat")), 1, _p(sun), stride, n_rays, w1.shape[0], _p(w1), _p(b1), _p(w2), _p(_chk(sky_rgb, "sky")),
-              _p(_chk(d_sky, "d_sky")), _p(g_w1), _p(g_b1), _p(g_w2), _p(g_b2), _p(_chk(d_t, "d_t")), _p(_chk(ts, "ts", torch.int64)), n_samples, tau,
-              _p(_chk(g_emb, "g_emb")), _p(_chk(params, "params")), _p(_chk(exp_avg, "exp_avg")), _p(_chk(exp_avg_sq, "exp_avg_sq")),
-              _p(_chk(late_idx, "late_idx", torch.int32)), late_idx.numel(), _p(_chk(state, "state")), float(lr), float(betas[0]), float(betas[1]),
-              float(eps), float(grad_scale), C.byref(ps) if ps is not None else None,
-              *_late_scratch(scratch, late_grad_scratch_bytes(n_rays, w1.shape[0], tau)), _stream())
+    args = _grad_tail_args(partial, plan, gidx, gscale, grad_flat, sun, w1, b1, w2, sky_rgb, d_sky, g_w1, g_b1, g_w2, g_b2, d_t, ts, n_rays,
+                           n_samples, tau, g_emb)
+    adam = _tail_adam_args(gidx.numel(), params, exp_avg, exp_avg_sq, late_idx, state, lr, betas, eps, grad_scale, pack)
+    need = late_grad_scratch_bytes(n_rays, w1.shape[0], tau)
+    _lib.call("sr_grad_tail_adam_det", C.byref(args), C.byref(adam), *_late_scratch(scratch, need), _stream())
 
 
 def _pack_scatter_struct(pack, n_model):

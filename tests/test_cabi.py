@@ -38,7 +38,7 @@ def test_every_declared_symbol_is_exported(handle):
 
 
 def test_version_and_stream_geometry(handle):
-    assert handle.sr_version() == 100
+    assert handle.sr_version() == 200
     for tau in (4, 16):
         m = packing.forward_maps(256, tau)
         assert handle.sr_fwd_stream_elems(256, tau) == m["idx"].size == m["scale"].size

@@ -38,7 +38,7 @@ def build_models(args, seeds=(1, 2), emb_seed=7):
 def test_native_library_is_loaded():
     from satnerf_amd import _lib
 
-    assert _lib.lib().sr_version() == 100
+    assert _lib.lib().sr_version() == 200
     maps = open("/proc/self/maps").read()
     assert "libsatrender.so" in maps
 

@@ -25,6 +25,7 @@ Offsets past 4 GiB: the 4-wave kernel steps 32-bit per-lane offsets, so workspac
 mlp_layout.h wgrad9_fits); test_r02_fallback_past_the_32_bit_bound runs it there.  wgrad.hip (SR_FMT16) needs no such case: every per-tile
 address is 64-bit pointer arithmetic (``prm.dpre + tile * kDpFrags * 64`` with a long tile), the per-lane offset handed to the DMA is
 below 1 KiB, and the partial-block index is (long)blockIdx.x * kWgBlockFloats."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -173,9 +174,12 @@ def check_grad_tail(feat, tau, partial, plan):
     for acc in (0, 1):
         base = torch.randn(gidx.numel(), device=DEV)
         grad = base.clone()
-        _lib.call("sr_grad_tail", ops._p(partial), ops._p(gidx), ops._p(gscale), gidx.numel(), ops._p(plan), plan.shape[0], ops._p(grad), acc,
-                  ops._p(sun), 3, 1, hidden, ops._p(w1), ops._p(b1), ops._p(w2), ops._p(sky), ops._p(d_sky), ops._p(g_w1), ops._p(g_b1), ops._p(g_w2),
-                  ops._p(g_b2), ops._p(d_t), ops._p(ts), 1, tau, ops._p(g_emb), ops._stream())
+        p = ops._p
+        args = _lib.GradTailArgs(partial=p(partial), gidx=p(gidx), gscale=p(gscale), n_params=gidx.numel(), blocks=p(plan), n_blocks=plan.shape[0],
+                                 grad=p(grad), accumulate=acc, sun=p(sun), sun_stride=3, n_rays=1, hidden=hidden, w1=p(w1), b1=p(b1), w2=p(w2),
+                                 sky=p(sky), d_sky=p(d_sky), g_w1=p(g_w1), g_b1=p(g_b1), g_w2=p(g_w2), g_b2=p(g_b2), d_t=p(d_t), ts=p(ts),
+                                 n_samples=1, tau=tau, g_emb=p(g_emb))
+        _lib.call("sr_grad_tail", C.byref(args), ops._stream())
         torch.cuda.synchronize()
         exp = want + (base.to(torch.float64) if acc else 0.0)
         extra = 2.0 ** -24 * exp.abs() if acc else 0.0
